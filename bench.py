@@ -9,7 +9,7 @@ block size 1024, gradient accumulation 8, Lion lr 1e-4 / wd 0.1, async grads
 (no gradient all-reduce), HF-default local grad clipping at 1.0, dropout 0.1.
 Data is synthetic (random token ids of that shape; no network).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 
 Every step is a full training step (8 micro-batches fwd+bwd, clip, vote
@@ -76,6 +76,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="after the timed steps rank 0 writes what the last step returned and left behind as "
+                         "DIR/<name>.npy (float32): loss, and a fixed seeded sample of the parameters and momenta")
+    ap.add_argument("--full", action="store_true",
+                    help="also run whatever the benchmark measures beyond the headline figure; a plain run only "
+                         "sets up, warms up, times --steps steps and prints the result line (nothing else is "
+                         "measured today: A/B runs, other tasks and profiles are separate invocations)")
     ap.add_argument("--task", default="clm", choices=sorted(PRESETS),
                     help="clm: GPT-2 pretraining (headline); sft: Llama-2-7B LoRA SFT (sft_llama2 config)")
     ap.add_argument("--model", default=None)
@@ -316,6 +323,42 @@ def build_reference(args, dev):
     return model, opt, cfg
 
 
+DUMP_BUDGET = 6 * 2**20  # sampled elements per dumped group (float32: 24 MB each, 48 MB + the loss in all)
+
+
+def _sample_flat(tensors, budget=DUMP_BUDGET, seed=20240):
+    """The tensors flattened and concatenated as float32 on the CPU; when that
+    is more than ``budget`` elements, a sample instead: from every tensor a
+    share proportional to its size (at least 1024 elements, or all of it), at
+    indices drawn from a generator seeded by the tensor's position, so two
+    runs -- or two builds -- sample the same elements."""
+    tensors = [t.detach() for t in tensors]
+    total = sum(t.numel() for t in tensors)
+    parts = []
+    for i, t in enumerate(tensors):
+        flat = t.reshape(-1)
+        k = flat.numel() if total <= budget else min(flat.numel(), max(1024, flat.numel() * budget // total))
+        if k < flat.numel():
+            g = torch.Generator().manual_seed(seed + i)
+            idx = torch.randint(0, flat.numel(), (k,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        parts.append(flat.float().cpu())
+    return torch.cat(parts).numpy() if parts else torch.zeros(0).numpy()
+
+
+def dump_outputs(path, loss, model, opt):
+    """What a caller of the timed step holds after the last one: the loss it
+    returned, the parameters it updated and the optimizer's momenta."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    params = [p for p in model.parameters() if p.requires_grad]
+    moms = [opt.state[p]["exp_avg"] for p in params if "exp_avg" in opt.state.get(p, {})]
+    np.save(os.path.join(path, "loss.npy"), loss.detach().float().reshape(1).cpu().numpy())
+    np.save(os.path.join(path, "params.npy"), _sample_flat(params))
+    np.save(os.path.join(path, "exp_avg.npy"), _sample_flat(moms))
+
+
 def main():
     args = parse()
     if os.environ.get("WORLD_SIZE") is None and args.gpus > 1:
@@ -449,6 +492,8 @@ def main():
     wire = wire_bytes_per_step(n_train, world, exchange)
     wire_meas = {k: stats.get(k, 0) // max(1, args.steps) for k in ("wire_bytes_sent", "wire_bytes_recv",
                                                                        "collectives")}
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, loss, model, opt)
     if rank == 0:
         out = {
             "metric": args.metric,

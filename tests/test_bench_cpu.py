@@ -45,6 +45,47 @@ def test_gpus3_without_torchrun_spawns_three_ranks():
     assert abs(out["value"] - 3 * 2 * 2 * 64 * 2 / (out["ms_per_step"] * 2 / 1000)) / out["value"] < 0.01
 
 
+def test_dump_outputs_repeatable_and_full_accepted(tmp_path):
+    """``--dump-outputs DIR`` writes the last timed step's loss and the sampled
+    parameters / momenta as float32 .npy files; the same arguments give the
+    same inputs and so (on the CPU, bit for bit) the same outputs.  ``--full``
+    is accepted and reports the same fields."""
+    import numpy as np
+
+    dumps = []
+    for tag, extra in (("a", ["--full"]), ("b", [])):
+        d = tmp_path / tag
+        r = _run(["--gpus", "1", "--device", "cpu", "--dump-outputs", str(d)] + extra + TINY)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
+        assert out["steps"] == 2 and out["ms_per_step"] > 0 and out["unit"] == "tokens/s"
+        arrs = {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))}
+        assert set(arrs) == {"loss", "params", "exp_avg"}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+        assert arrs["loss"].shape == (1,) and abs(float(arrs["loss"][0]) - out["loss"]) < 1e-3
+        assert arrs["params"].size == arrs["exp_avg"].size > 0 and np.abs(arrs["exp_avg"]).max() > 0
+        assert sum(a.nbytes for a in arrs.values()) <= 64 * 2**20
+        dumps.append(arrs)
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
+
+
+def test_dump_sample_is_fixed_and_bounded():
+    """Outputs larger than the budget are sampled: the same elements every
+    time, every tensor represented, within the budget plus the per-tensor floor."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    ts = [torch.arange(50000, dtype=torch.bfloat16), torch.arange(100.0), torch.arange(3000.0).view(30, 100)]
+    a = bench._sample_flat(ts, budget=10000)
+    b = bench._sample_flat(ts, budget=10000)
+    assert a.dtype.name == "float32" and (a == b).all()
+    assert 100 + 1024 < a.size <= 10000 + 3 * 1024
+    assert (a[-1024:] < 3000).all() and (a[-1124:-1024] == torch.arange(100.0).numpy()).all()
+    full = bench._sample_flat(ts, budget=10**6)
+    assert full.size == 53100
+
+
 def test_world_size_mismatch_is_an_error():
     r = _run(["--gpus", "2", "--device", "cpu", "--backend", "gloo"] + TINY,
              env={"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})

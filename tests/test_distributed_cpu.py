@@ -1,9 +1,7 @@
 """Multi-process (gloo, CPU) tests of the distributed Lion step: every exchange
 strategy against the per-tensor oracle, replica consistency, tie rules,
 simulated worker dropout, the stochastic path and reference parity."""
-import importlib.util
 import os
-import sys
 
 import pytest
 import torch
@@ -11,7 +9,7 @@ import torch.distributed as dist
 
 from dist_utils import run_world
 
-REF_PATH = "/root/reference/distributed_lion.py"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def _model(seed=0, dtype=torch.bfloat16):
@@ -163,28 +161,29 @@ def test_stochastic_binarization_runs_and_replicas_agree():
 
 
 def _reference_parity(rank, world):
-    sys.dont_write_bytecode = True
-    spec = importlib.util.spec_from_file_location("_ref_dl", REF_PATH)
-    R = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(R)
+    """The reference's run, recorded by tools/make_reference_golden.py: this
+    rank's gradients of each step go through Lion, the parameters after every
+    step must be the ones the reference's replicas held."""
     from distributed_lion_pytorch_amd import Lion
 
-    a, b = _model(3), _model(3)
+    gold = torch.load(os.path.join(GOLDEN, f"lion_reference_w{world}.pt"), weights_only=True)
+    assert gold["world"] == world and len(gold["grads"]) == world
+    b = _model(3)
+    b.load_state_dict(gold["init"])
     # lr exactly representable in bf16: on CPU, ATen rounds `alpha` of a bf16
     # add_ to bf16 while the GPU kernels (like ATen-HIP) keep it in fp32.
-    lr = 2.0 ** -7
-    oa = R.Lion(a.parameters(), lr=lr, weight_decay=0.1)
-    ob = Lion(b.parameters(), lr=lr, weight_decay=0.1, exchange="a2a")
-    for step in range(3):
-        x = _batch(rank, step)
-        for net, opt in ((a, oa), (b, ob)):
-            opt.zero_grad()
-            _loss(net, x).backward()
-            opt.step()
-    return all(torch.equal(x, y) for x, y in zip(a.parameters(), b.parameters()))
+    assert gold["lr"] == 2.0 ** -7
+    ob = Lion(b.parameters(), lr=gold["lr"], weight_decay=gold["weight_decay"], exchange="a2a")
+    ok = len(gold["params"]) == 3
+    for grads, params in zip(gold["grads"][rank], gold["params"]):
+        ob.zero_grad()
+        for p, g in zip(b.parameters(), grads):
+            p.grad = g.clone()
+        ob.step()
+        ok = ok and all(torch.equal(x, y) for x, y in zip(params, b.parameters()))
+    return ok and all(torch.equal(m, ob.state[p]["exp_avg"]) for m, p in zip(gold["exp_avg"][rank], b.parameters()))
 
 
-@pytest.mark.skipif(not os.path.exists(REF_PATH), reason="reference not mounted")
 @pytest.mark.parametrize("world", [2, 3])
 def test_bit_parity_with_reference_distributed(world):
     assert all(run_world(_reference_parity, world))
