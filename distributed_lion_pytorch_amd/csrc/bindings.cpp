@@ -303,6 +303,12 @@ void check_rows(const Tensor& t, const char* name, int64_t C) {
   TORCH_CHECK(t.size(-1) == C, "dlion norm: ", name, " last dim mismatch");
 }
 
+// the add+norm kernels hold a row in registers as 8-byte lane chunks (csrc/norm_kernels.hip)
+void check_norm_width(int64_t C) {
+  TORCH_CHECK(C >= 256 && C <= 8192 && C % 8 == 0,
+              "dlion norm: hidden size must satisfy 256 <= C <= 8192 and C % 8 == 0, got ", C);
+}
+
 std::pair<uint32_t, float> drop_params(double p) {
   uint32_t th = static_cast<uint32_t>(std::llround(p * 65536.0));
   if (th > 65535u) th = 65535u;
@@ -317,8 +323,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> add_norm_fwd(const Tensor& x, const s
   const int64_t C = x.size(-1), rows = x.numel() / C;
   check_rows(x, "x", C);
   check_rows(gamma, "gamma", C);
-  TORCH_CHECK((C % 256 == 0 && C <= 1024) || (C % 1024 == 0 && C >= 2048 && C <= 8192 && C != 7168),
-              "dlion norm: hidden size must be one of 256, 512, 768, 1024, 2048, 3072, 4096, 5120, 6144, 8192");
+  check_norm_width(C);
   TORCH_CHECK(rms || beta.has_value(), "dlion norm: LayerNorm needs beta");
   if (y.has_value()) check_rows(*y, "y", C);
   if (bias.has_value()) check_rows(*bias, "bias", C);
@@ -347,6 +352,7 @@ std::tuple<Tensor, Tensor, Tensor> add_norm_bwd(const Tensor& dh, const std::opt
   check_rows(dh, "dh", C);
   check_rows(xo, "xo", C);
   check_rows(gamma, "gamma", C);
+  check_norm_width(C);
   if (dxo_in.has_value()) check_rows(*dxo_in, "dxo_in", C);
   const c10::DeviceGuard g(xo.device());
   auto dx = at::empty_like(xo);

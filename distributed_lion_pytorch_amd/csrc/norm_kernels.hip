@@ -18,6 +18,13 @@
 // wide Llama rows (C = 2048..8192); 4 consecutive bf16 (8 bytes) per lane per
 // step, the whole row held in registers.  The dropout keep-mask is a stateless hash of
 // (seed, row * C + col) at 16-bit resolution -- regenerated, never stored.
+//
+// Widths: the ten exact widths C = NS*4*64*WPR run with C as a compile-time
+// constant (TAIL = false).  Every other C with 256 <= C <= 8192, C % 8 == 0 runs
+// the TAIL = true form of the smallest capacity CAP = NS*4*64*WPR >= C with a
+// runtime C: a lane's 8-byte chunk lies wholly inside or wholly outside the
+// row, so one predicate per chunk masks its loads and stores; a masked chunk
+// holds zeros, which the row math carries branch-free.
 #include "common.h"
 #include "kernels.h"
 
@@ -29,13 +36,6 @@ namespace dlion {
 __device__ __forceinline__ float wsum(float v) { return wave_sum_dpp(v); }
 
 __device__ __forceinline__ void unpack4(const uint2 v, float (&o)[4]) {
-  o[0] = bf16_to_f32(v.x & 0xffffu);
-  o[1] = bf16_to_f32(v.x >> 16);
-  o[2] = bf16_to_f32(v.y & 0xffffu);
-  o[3] = bf16_to_f32(v.y >> 16);
-}
-__device__ __forceinline__ void ld4(const uint16_t* p, float (&o)[4]) {
-  const uint2 v = *reinterpret_cast<const uint2*>(p);
   o[0] = bf16_to_f32(v.x & 0xffffu);
   o[1] = bf16_to_f32(v.x >> 16);
   o[2] = bf16_to_f32(v.y & 0xffffu);
@@ -57,14 +57,32 @@ __device__ __forceinline__ void st4(uint16_t* p, const float (&o)[4]) {
 
 // Row groups: WPR waves cooperate on one row (WPR = 1 for C <= 1024; 2..8 for
 // the wide Llama rows, C = 2048 .. 8192), so a lane holds NS*4 <= 16 values of
-// a row in registers.  C = NS * 4 * 64 * WPR; column of chunk k for group
-// thread tg: k * 256 * WPR + tg * 4.  Blocks are 4 waves of 4 rows when
-// WPR = 1, else WPR waves of one row.
+// a row in registers.  Capacity CAP = NS * 4 * 64 * WPR (= C unless TAIL);
+// column of chunk k for group thread tg: k * 256 * WPR + tg * 4.  Blocks are
+// 4 waves of 4 rows when WPR = 1, else WPR waves of one row.
 template <int WPR>
 struct RowGroup {
   static constexpr int kWaves = WPR == 1 ? 4 : WPR;  // waves per block
   static constexpr int kRows = kWaves / WPR;         // rows per block
 };
+// is the chunk at column c inside the row?  Always, at compile time, for the
+// exact widths.
+template <bool TAIL>
+__device__ __forceinline__ bool chunk_live(int c, int C) {
+  if constexpr (TAIL) return c < C;
+  else return true;
+}
+__device__ __forceinline__ uint2 ldparam(const uint16_t* p) { return *reinterpret_cast<const uint2*>(p); }
+// A masked chunk loads nothing and holds zeros.  (Loading a clamped in-row
+// address instead and selecting zero afterwards drops the exec-mask regions
+// but was measured slower: the masked lanes' loads still occupy the memory pipe.)
+__device__ __forceinline__ uint2 ldrow_sel(const uint16_t* p, int c, bool live) {
+  return live ? ldrow(p + c) : make_uint2(0u, 0u);
+}
+__device__ __forceinline__ uint2 ldparam_sel(const uint16_t* p, int c, bool live) {
+  return live ? ldparam(p + c) : make_uint2(0u, 0u);
+}
+
 template <int WPR>
 __device__ __forceinline__ float2 gsum2(float a, float b, float2* scratch) {
   a = wsum(a);
@@ -87,14 +105,17 @@ __device__ __forceinline__ float2 gsum2(float a, float b, float2* scratch) {
 }
 
 // --------------------------------------------------------------------- forward
-// y may be null (plain norm of x), bias may be null.
-template <int NS, int WPR, bool RMS>
-__global__ void __launch_bounds__(64 * RowGroup<WPR>::kWaves)
-add_norm_fwd_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ y, const uint16_t* __restrict__ bias,
-                    const uint16_t* __restrict__ gamma, const uint16_t* __restrict__ beta, uint16_t* __restrict__ xo,
-                    uint16_t* __restrict__ h, float* __restrict__ mean_out, float* __restrict__ rstd_out, int64_t rows,
-                    float eps, uint32_t seed, uint32_t thresh16, float inv_keep) {
-  constexpr int G = 64 * WPR, C = NS * 4 * G;
+// y may be null (plain norm of x), bias may be null.  Cr: the row width, read
+// only when TAIL (masked chunks hold zeros and are never loaded or stored).
+template <int NS, int WPR, bool RMS, bool TAIL>
+__device__ __forceinline__ void
+add_norm_fwd_body(const uint16_t* __restrict__ x, const uint16_t* __restrict__ y, const uint16_t* __restrict__ bias,
+                  const uint16_t* __restrict__ gamma, const uint16_t* __restrict__ beta, uint16_t* __restrict__ xo,
+                  uint16_t* __restrict__ h, float* __restrict__ mean_out, float* __restrict__ rstd_out, int64_t rows,
+                  float eps, uint32_t seed, uint32_t thresh16, float inv_keep, int Cr) {
+  constexpr int G = 64 * WPR, CAP = NS * 4 * G;
+  const int C = TAIL ? Cr : CAP;
+  const float inv_c = TAIL ? 1.f / static_cast<float>(C) : 1.f / CAP;
   __shared__ float2 scratch[WPR];
   const int tg = threadIdx.x % G;
   const int64_t row = static_cast<int64_t>(blockIdx.x) * RowGroup<WPR>::kRows + threadIdx.x / G;
@@ -105,20 +126,31 @@ add_norm_fwd_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__
   // trips per row); gamma / beta too, ahead of the reductions
   uint2 rx[NS], ry[NS], rb[NS], rg[NS], re[NS];
 #pragma unroll
-  for (int k = 0; k < NS; ++k) rx[k] = ldrow(x + base + k * 4 * G + tg * 4);
+  for (int k = 0; k < NS; ++k) {
+    const int c = k * 4 * G + tg * 4;
+    rx[k] = ldrow_sel(x + base, c, chunk_live<TAIL>(c, C));
+  }
   const bool has_y = y != nullptr, has_b = has_y && bias != nullptr;
   if (has_y) {
 #pragma unroll
-    for (int k = 0; k < NS; ++k) ry[k] = ldrow(y + base + k * 4 * G + tg * 4);
+    for (int k = 0; k < NS; ++k) {
+      const int c = k * 4 * G + tg * 4;
+      ry[k] = ldrow_sel(y + base, c, chunk_live<TAIL>(c, C));
+    }
   }
   if (has_b) {
 #pragma unroll
-    for (int k = 0; k < NS; ++k) rb[k] = *reinterpret_cast<const uint2*>(bias + k * 4 * G + tg * 4);
+    for (int k = 0; k < NS; ++k) {
+      const int c = k * 4 * G + tg * 4;
+      rb[k] = ldparam_sel(bias, c, chunk_live<TAIL>(c, C));
+    }
   }
 #pragma unroll
   for (int k = 0; k < NS; ++k) {
-    rg[k] = *reinterpret_cast<const uint2*>(gamma + k * 4 * G + tg * 4);
-    if constexpr (!RMS) re[k] = *reinterpret_cast<const uint2*>(beta + k * 4 * G + tg * 4);
+    const int c = k * 4 * G + tg * 4;
+    const bool live = chunk_live<TAIL>(c, C);
+    rg[k] = ldparam_sel(gamma, c, live);
+    if constexpr (!RMS) re[k] = ldparam_sel(beta, c, live);
   }
   float v[NS][4];
   float s = 0.f;
@@ -136,22 +168,24 @@ add_norm_fwd_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__
         const float add = ((kp >> j) & 1u) ? (yv[j] + bv[j]) * inv_keep : 0.f;
         v[k][j] = bf16_to_f32(f32_to_bf16(v[k][j] + add));  // residual stream is stored in bf16
       }
-      st4(xo + base + c, v[k]);
+      if (chunk_live<TAIL>(c, C)) st4(xo + base + c, v[k]);
     }
 #pragma unroll
-    for (int j = 0; j < 4; ++j) s += v[k][j];
+    for (int j = 0; j < 4; ++j) s += v[k][j];  // a masked chunk adds zeros
   }
   float mean = 0.f;
-  if constexpr (!RMS) mean = gsum2<WPR>(s, 0.f, scratch).x * (1.f / C);
+  if constexpr (!RMS) mean = gsum2<WPR>(s, 0.f, scratch).x * inv_c;
   float q = 0.f;
 #pragma unroll
-  for (int k = 0; k < NS; ++k)
+  for (int k = 0; k < NS; ++k) {
+    const bool live = chunk_live<TAIL>(k * 4 * G + tg * 4, C);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const float d = v[k][j] - mean;
+      const float d = live ? v[k][j] - mean : 0.f;  // a masked element adds 0, not (0 - mean)^2
       q += d * d;
     }
-  const float rstd = rsqrtf(gsum2<WPR>(q, 0.f, scratch).x * (1.f / C) + eps);
+  }
+  const float rstd = rsqrtf(gsum2<WPR>(q, 0.f, scratch).x * inv_c + eps);
 #pragma unroll
   for (int k = 0; k < NS; ++k) {
     const int c = k * 4 * G + tg * 4;
@@ -160,7 +194,7 @@ add_norm_fwd_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__
     if constexpr (!RMS) unpack4(re[k], b);
 #pragma unroll
     for (int j = 0; j < 4; ++j) o[j] = (v[k][j] - mean) * rstd * g[j] + b[j];
-    st4(h + base + c, o);
+    if (chunk_live<TAIL>(c, C)) st4(h + base + c, o);
   }
   if (tg == 0) {
     mean_out[row] = mean;
@@ -168,25 +202,48 @@ add_norm_fwd_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__
   }
 }
 
+#define NORM_FWD_PARAMS                                                                                          \
+  const uint16_t *__restrict__ x, const uint16_t *__restrict__ y, const uint16_t *__restrict__ bias,             \
+      const uint16_t *__restrict__ gamma, const uint16_t *__restrict__ beta, uint16_t *__restrict__ xo,          \
+      uint16_t *__restrict__ h, float *__restrict__ mean_out, float *__restrict__ rstd_out, int64_t rows,        \
+      float eps, uint32_t seed, uint32_t thresh16, float inv_keep
+#define NORM_FWD_ARGS x, y, bias, gamma, beta, xo, h, mean_out, rstd_out, rows, eps, seed, thresh16, inv_keep
+// exact width C = NS*4*64*WPR
+template <int NS, int WPR, bool RMS>
+__global__ void __launch_bounds__(64 * RowGroup<WPR>::kWaves) add_norm_fwd_kernel(NORM_FWD_PARAMS) {
+  add_norm_fwd_body<NS, WPR, RMS, false>(NORM_FWD_ARGS, NS * 4 * 64 * WPR);
+}
+// any C <= NS*4*64*WPR with C % 4 == 0
+template <int NS, int WPR, bool RMS>
+__global__ void __launch_bounds__(64 * RowGroup<WPR>::kWaves) add_norm_fwd_tail_kernel(NORM_FWD_PARAMS, int C) {
+  add_norm_fwd_body<NS, WPR, RMS, true>(NORM_FWD_ARGS, C);
+}
+
 // -------------------------------------------------------------------- backward
 // xo: the normalised input (the residual stream after the add); dxo_in: the
 // residual-stream gradient from later layers (nullable).  Outputs: dx (residual
 // grad), dy (branch grad, nullable for a plain norm).  part: [gridDim.x][3][C]
-// fp32 partial sums of dgamma, dbeta, dbias (= sum dy) for this block's rows.
-template <int NS, int WPR, bool RMS>
-__global__ void __launch_bounds__(64 * RowGroup<WPR>::kWaves)
-add_norm_bwd_kernel(const uint16_t* __restrict__ dh, const uint16_t* __restrict__ dxo_in,
-                    const uint16_t* __restrict__ xo, const uint16_t* __restrict__ gamma,
-                    const float* __restrict__ mean_in, const float* __restrict__ rstd_in, uint16_t* __restrict__ dx,
-                    uint16_t* __restrict__ dy, float* __restrict__ part, int64_t rows, uint32_t seed,
-                    uint32_t thresh16, float inv_keep) {
-  constexpr int G = 64 * WPR, C = NS * 4 * G, RPB = RowGroup<WPR>::kRows;
+// fp32 partial sums of dgamma, dbeta, dbias (= sum dy) for this block's rows;
+// C is the runtime width when TAIL, so a masked chunk must never be written
+// there (column c >= C of one section is another section, or another block).
+template <int NS, int WPR, bool RMS, bool TAIL>
+__device__ __forceinline__ void
+add_norm_bwd_body(const uint16_t* __restrict__ dh, const uint16_t* __restrict__ dxo_in,
+                  const uint16_t* __restrict__ xo, const uint16_t* __restrict__ gamma,
+                  const float* __restrict__ mean_in, const float* __restrict__ rstd_in, uint16_t* __restrict__ dx,
+                  uint16_t* __restrict__ dy, float* __restrict__ part, int64_t rows, uint32_t seed,
+                  uint32_t thresh16, float inv_keep, int Cr) {
+  constexpr int G = 64 * WPR, CAP = NS * 4 * G, RPB = RowGroup<WPR>::kRows;
+  const int C = TAIL ? Cr : CAP;
+  const float inv_c = TAIL ? 1.f / static_cast<float>(C) : 1.f / CAP;
   __shared__ float2 scratch[WPR];
   const int tg = threadIdx.x % G, grp = threadIdx.x / G;
+  bool live[NS];
   float gacc[NS][4], bacc[NS][4], yacc[NS][4], g[NS][4];
 #pragma unroll
   for (int k = 0; k < NS; ++k) {
-    ld4(gamma + k * 4 * G + tg * 4, g[k]);
+    live[k] = chunk_live<TAIL>(k * 4 * G + tg * 4, C);
+    unpack4(ldparam_sel(gamma, k * 4 * G + tg * 4, live[k]), g[k]);
 #pragma unroll
     for (int j = 0; j < 4; ++j) gacc[k][j] = bacc[k][j] = yacc[k][j] = 0.f;
   }
@@ -202,9 +259,9 @@ add_norm_bwd_kernel(const uint16_t* __restrict__ dh, const uint16_t* __restrict_
 #pragma unroll
     for (int k = 0; k < NS; ++k) {
       const int c = k * 4 * G + tg * 4;
-      nxo[k] = ldrow(xo + b + c);
-      ndh[k] = ldrow(dh + b + c);
-      if (dxo_in != nullptr) ndx[k] = ldrow(dxo_in + b + c);
+      nxo[k] = ldrow_sel(xo + b, c, live[k]);
+      ndh[k] = ldrow_sel(dh + b, c, live[k]);
+      if (dxo_in != nullptr) ndx[k] = ldrow_sel(dxo_in + b, c, live[k]);
     }
     nmean = RMS ? 0.f : mean_in[r];
     nrstd = rstd_in[r];
@@ -226,6 +283,8 @@ add_norm_bwd_kernel(const uint16_t* __restrict__ dh, const uint16_t* __restrict_
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int k = 0; k < NS; ++k) {
+      // a masked chunk holds dh = gamma = 0: gd and every term it adds to
+      // s1 / s2 / gacc / bacc is an exact zero, without a branch
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         xh[k][j] = (cxo[k][j] - mean) * rstd;
@@ -237,9 +296,10 @@ add_norm_bwd_kernel(const uint16_t* __restrict__ dh, const uint16_t* __restrict_
       }
     }
     const float2 ms = gsum2<WPR>(RMS ? 0.f : s1, s2, scratch);
-    const float m1 = ms.x * (1.f / C), m2 = ms.y * (1.f / C);
+    const float m1 = ms.x * inv_c, m2 = ms.y * inv_c;
 #pragma unroll
     for (int k = 0; k < NS; ++k) {
+      if (!live[k]) continue;
       const int c = k * 4 * G + tg * 4;
       float t[4];
 #pragma unroll
@@ -258,37 +318,40 @@ add_norm_bwd_kernel(const uint16_t* __restrict__ dh, const uint16_t* __restrict_
     }
   }
   float4* out = reinterpret_cast<float4*>(part + static_cast<int64_t>(blockIdx.x) * 3 * C);
+  const int sec1 = C / 4, sec2 = C / 2;  // dbeta / dbias sections, in float4 units of the runtime C
   if constexpr (RPB == 1) {
     // one row group per block: every thread owns distinct columns
 #pragma unroll
     for (int k = 0; k < NS; ++k) {
+      if (!live[k]) continue;
       const int c4 = k * G + tg;
       out[c4] = make_float4(gacc[k][0], gacc[k][1], gacc[k][2], gacc[k][3]);
-      out[C / 4 + c4] = make_float4(bacc[k][0], bacc[k][1], bacc[k][2], bacc[k][3]);
-      out[C / 2 + c4] = make_float4(yacc[k][0], yacc[k][1], yacc[k][2], yacc[k][3]);
+      out[sec1 + c4] = make_float4(bacc[k][0], bacc[k][1], bacc[k][2], bacc[k][3]);
+      out[sec2 + c4] = make_float4(yacc[k][0], yacc[k][1], yacc[k][2], yacc[k][3]);
     }
   } else {
     // fold the block's RPB row groups into one partial row triple: groups
     // RPB-1 .. 1 accumulate into one LDS row triple in turn (each thread
     // touches only its own columns), group 0 adds it and stores
-    __shared__ float4 red[3 * C / 4];
+    __shared__ float4 red[3 * CAP / 4];  // sized by the capacity, laid out by the runtime C
     for (int src = RPB - 1; src >= 1; --src) {
       if (grp == src) {
 #pragma unroll
         for (int k = 0; k < NS; ++k) {
+          if (!live[k]) continue;
           const int c4 = k * G + tg;
           float4 a = make_float4(gacc[k][0], gacc[k][1], gacc[k][2], gacc[k][3]);
           float4 b = make_float4(bacc[k][0], bacc[k][1], bacc[k][2], bacc[k][3]);
           float4 d = make_float4(yacc[k][0], yacc[k][1], yacc[k][2], yacc[k][3]);
           if (src != RPB - 1) {
-            const float4 a0 = red[c4], b0 = red[C / 4 + c4], d0 = red[C / 2 + c4];
+            const float4 a0 = red[c4], b0 = red[sec1 + c4], d0 = red[sec2 + c4];
             a.x += a0.x; a.y += a0.y; a.z += a0.z; a.w += a0.w;
             b.x += b0.x; b.y += b0.y; b.z += b0.z; b.w += b0.w;
             d.x += d0.x; d.y += d0.y; d.z += d0.z; d.w += d0.w;
           }
           red[c4] = a;
-          red[C / 4 + c4] = b;
-          red[C / 2 + c4] = d;
+          red[sec1 + c4] = b;
+          red[sec2 + c4] = d;
         }
       }
       __syncthreads();
@@ -296,36 +359,92 @@ add_norm_bwd_kernel(const uint16_t* __restrict__ dh, const uint16_t* __restrict_
     if (grp == 0) {
 #pragma unroll
       for (int k = 0; k < NS; ++k) {
+        if (!live[k]) continue;
         const int c4 = k * G + tg;
-        const float4 a0 = red[c4], b0 = red[C / 4 + c4], d0 = red[C / 2 + c4];
+        const float4 a0 = red[c4], b0 = red[sec1 + c4], d0 = red[sec2 + c4];
         out[c4] = make_float4(gacc[k][0] + a0.x, gacc[k][1] + a0.y, gacc[k][2] + a0.z, gacc[k][3] + a0.w);
-        out[C / 4 + c4] = make_float4(bacc[k][0] + b0.x, bacc[k][1] + b0.y, bacc[k][2] + b0.z, bacc[k][3] + b0.w);
-        out[C / 2 + c4] = make_float4(yacc[k][0] + d0.x, yacc[k][1] + d0.y, yacc[k][2] + d0.z, yacc[k][3] + d0.w);
+        out[sec1 + c4] = make_float4(bacc[k][0] + b0.x, bacc[k][1] + b0.y, bacc[k][2] + b0.z, bacc[k][3] + b0.w);
+        out[sec2 + c4] = make_float4(yacc[k][0] + d0.x, yacc[k][1] + d0.y, yacc[k][2] + d0.z, yacc[k][3] + d0.w);
       }
     }
   }
 }
 
+#define NORM_BWD_PARAMS                                                                                          \
+  const uint16_t *__restrict__ dh, const uint16_t *__restrict__ dxo_in, const uint16_t *__restrict__ xo,         \
+      const uint16_t *__restrict__ gamma, const float *__restrict__ mean_in, const float *__restrict__ rstd_in,  \
+      uint16_t *__restrict__ dx, uint16_t *__restrict__ dy, float *__restrict__ part, int64_t rows,              \
+      uint32_t seed, uint32_t thresh16, float inv_keep
+#define NORM_BWD_ARGS dh, dxo_in, xo, gamma, mean_in, rstd_in, dx, dy, part, rows, seed, thresh16, inv_keep
+template <int NS, int WPR, bool RMS>
+__global__ void __launch_bounds__(64 * RowGroup<WPR>::kWaves) add_norm_bwd_kernel(NORM_BWD_PARAMS) {
+  add_norm_bwd_body<NS, WPR, RMS, false>(NORM_BWD_ARGS, NS * 4 * 64 * WPR);
+}
+template <int NS, int WPR, bool RMS>
+__global__ void __launch_bounds__(64 * RowGroup<WPR>::kWaves) add_norm_bwd_tail_kernel(NORM_BWD_PARAMS, int C) {
+  add_norm_bwd_body<NS, WPR, RMS, true>(NORM_BWD_ARGS, C);
+}
+
 // ------------------------------------------------------------------ launchers
-// (WPR, NS) shapes: C = 256..1024 one wave per row; C = 2048..8192 (multiples
-// of 1024) one WPR-wave block per row.  Anything else -> hipErrorInvalidValue
-// (the Python side checks norm_supported() first and uses ATen otherwise).
+// Exact widths (TAIL = false): C = 256..1024 one wave per row; C = 2048..8192
+// (multiples of 1024, without 7168) one WPR-wave block per row.  Any other
+// 256 <= C <= 8192 with C % 8 == 0 takes the TAIL form of the smallest
+// capacity that holds it: C < 1024 one wave per row with NS = ceil(C / 256),
+// wider WPR = ceil(C / 1024) waves with NS = 4 (ops/fused.norm_supported and
+// _norm_parts mirror this rule).  Anything else -> hipErrorInvalidValue.
+#define NORM_CASE(V, NS_, WPR_, TAIL_, ...)                                       \
+  case V: { constexpr int NS = NS_, WPR = WPR_; constexpr bool TAIL = TAIL_; __VA_ARGS__; break; }
 #define NORM_DISPATCH(C_VAL, ...)                                                 \
   switch (C_VAL) {                                                                \
-    case 256: { constexpr int NS = 1, WPR = 1; __VA_ARGS__; break; }             \
-    case 512: { constexpr int NS = 2, WPR = 1; __VA_ARGS__; break; }             \
-    case 768: { constexpr int NS = 3, WPR = 1; __VA_ARGS__; break; }             \
-    case 1024: { constexpr int NS = 4, WPR = 1; __VA_ARGS__; break; }            \
-    case 2048: { constexpr int NS = 4, WPR = 2; __VA_ARGS__; break; }            \
-    case 3072: { constexpr int NS = 4, WPR = 3; __VA_ARGS__; break; }            \
-    case 4096: { constexpr int NS = 4, WPR = 4; __VA_ARGS__; break; }            \
-    case 5120: { constexpr int NS = 4, WPR = 5; __VA_ARGS__; break; }            \
-    case 6144: { constexpr int NS = 4, WPR = 6; __VA_ARGS__; break; }            \
-    case 8192: { constexpr int NS = 4, WPR = 8; __VA_ARGS__; break; }            \
-    default: return hipErrorInvalidValue;                                         \
+    NORM_CASE(256, 1, 1, false, __VA_ARGS__)                                      \
+    NORM_CASE(512, 2, 1, false, __VA_ARGS__)                                      \
+    NORM_CASE(768, 3, 1, false, __VA_ARGS__)                                      \
+    NORM_CASE(1024, 4, 1, false, __VA_ARGS__)                                     \
+    NORM_CASE(2048, 4, 2, false, __VA_ARGS__)                                     \
+    NORM_CASE(3072, 4, 3, false, __VA_ARGS__)                                     \
+    NORM_CASE(4096, 4, 4, false, __VA_ARGS__)                                     \
+    NORM_CASE(5120, 4, 5, false, __VA_ARGS__)                                     \
+    NORM_CASE(6144, 4, 6, false, __VA_ARGS__)                                     \
+    NORM_CASE(8192, 4, 8, false, __VA_ARGS__)                                     \
+    default:                                                                      \
+      if ((C_VAL) < 256 || (C_VAL) > 8192 || (C_VAL) % 8 != 0) return hipErrorInvalidValue; \
+      if ((C_VAL) < 1024) {                                                       \
+        switch (((C_VAL) + 255) / 256) {                                          \
+          NORM_CASE(2, 2, 1, true, __VA_ARGS__)                                   \
+          NORM_CASE(3, 3, 1, true, __VA_ARGS__)                                   \
+          NORM_CASE(4, 4, 1, true, __VA_ARGS__)                                   \
+          default: return hipErrorInvalidValue;                                   \
+        }                                                                         \
+      } else {                                                                    \
+        switch (((C_VAL) + 1023) / 1024) {                                        \
+          NORM_CASE(2, 4, 2, true, __VA_ARGS__)                                   \
+          NORM_CASE(3, 4, 3, true, __VA_ARGS__)                                   \
+          NORM_CASE(4, 4, 4, true, __VA_ARGS__)                                   \
+          NORM_CASE(5, 4, 5, true, __VA_ARGS__)                                   \
+          NORM_CASE(6, 4, 6, true, __VA_ARGS__)                                   \
+          NORM_CASE(7, 4, 7, true, __VA_ARGS__)                                   \
+          NORM_CASE(8, 4, 8, true, __VA_ARGS__)                                   \
+          default: return hipErrorInvalidValue;                                   \
+        }                                                                         \
+      }                                                                           \
   }
 
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// one instantiation per (NS, WPR, RMS) that NORM_DISPATCH names: the exact
+// kernel or the tail kernel, never both
+template <int NS, int WPR, bool RMS, bool TAIL, typename... Args>
+static void norm_fwd_launch(int64_t rows, int C, hipStream_t st, Args... args) {
+  const dim3 grid(ceil_div(rows, RowGroup<WPR>::kRows)), block(64 * RowGroup<WPR>::kWaves);
+  if constexpr (TAIL) hipLaunchKernelGGL((add_norm_fwd_tail_kernel<NS, WPR, RMS>), grid, block, 0, st, args..., C);
+  else hipLaunchKernelGGL((add_norm_fwd_kernel<NS, WPR, RMS>), grid, block, 0, st, args...);
+}
+template <int NS, int WPR, bool RMS, bool TAIL, typename... Args>
+static void norm_bwd_launch(int parts, int C, hipStream_t st, Args... args) {
+  const dim3 grid(parts), block(64 * RowGroup<WPR>::kWaves);
+  if constexpr (TAIL) hipLaunchKernelGGL((add_norm_bwd_tail_kernel<NS, WPR, RMS>), grid, block, 0, st, args..., C);
+  else hipLaunchKernelGGL((add_norm_bwd_kernel<NS, WPR, RMS>), grid, block, 0, st, args...);
+}
 
 hipError_t launch_add_norm_fwd(const void* x, const void* y, const void* bias, const void* gamma, const void* beta,
                                void* xo, void* h, float* mean, float* rstd, int64_t rows, int C, float eps, bool rms,
@@ -338,13 +457,11 @@ hipError_t launch_add_norm_fwd(const void* x, const void* y, const void* bias, c
   auto XO = static_cast<uint16_t*>(xo);
   auto H = static_cast<uint16_t*>(h);
   if (rms) {
-    NORM_DISPATCH(C, hipLaunchKernelGGL((add_norm_fwd_kernel<NS, WPR, true>), dim3(ceil_div(rows, RowGroup<WPR>::kRows)),
-                                        dim3(64 * RowGroup<WPR>::kWaves), 0, st, X, Y, Bi, G, Bt, XO, H, mean, rstd, rows, eps, seed, thresh16,
-                                        inv_keep));
+    NORM_DISPATCH(C, norm_fwd_launch<NS, WPR, true, TAIL>(rows, C, st, X, Y, Bi, G, Bt, XO, H, mean, rstd, rows, eps, seed,
+                                                          thresh16, inv_keep));
   } else {
-    NORM_DISPATCH(C, hipLaunchKernelGGL((add_norm_fwd_kernel<NS, WPR, false>), dim3(ceil_div(rows, RowGroup<WPR>::kRows)),
-                                        dim3(64 * RowGroup<WPR>::kWaves), 0, st, X, Y, Bi, G, Bt, XO, H, mean, rstd, rows, eps, seed, thresh16,
-                                        inv_keep));
+    NORM_DISPATCH(C, norm_fwd_launch<NS, WPR, false, TAIL>(rows, C, st, X, Y, Bi, G, Bt, XO, H, mean, rstd, rows, eps, seed,
+                                                           thresh16, inv_keep));
   }
   return hipGetLastError();
 }
@@ -352,7 +469,6 @@ hipError_t launch_add_norm_fwd(const void* x, const void* y, const void* bias, c
 hipError_t launch_add_norm_bwd(const void* dh, const void* dxo_in, const void* xo, const void* gamma, const float* mean,
                                const float* rstd, void* dx, void* dy, float* part, int parts, int64_t rows, int C,
                                bool rms, uint32_t seed, uint32_t thresh16, float inv_keep, hipStream_t st) {
-  const dim3 grid(parts);
   auto DH = static_cast<const uint16_t*>(dh);
   auto DXI = static_cast<const uint16_t*>(dxo_in);
   auto XO = static_cast<const uint16_t*>(xo);
@@ -360,11 +476,11 @@ hipError_t launch_add_norm_bwd(const void* dh, const void* dxo_in, const void* x
   auto DX = static_cast<uint16_t*>(dx);
   auto DY = static_cast<uint16_t*>(dy);
   if (rms) {
-    NORM_DISPATCH(C, hipLaunchKernelGGL((add_norm_bwd_kernel<NS, WPR, true>), grid, dim3(64 * RowGroup<WPR>::kWaves), 0, st, DH, DXI, XO, G,
-                                        mean, rstd, DX, DY, part, rows, seed, thresh16, inv_keep));
+    NORM_DISPATCH(C, norm_bwd_launch<NS, WPR, true, TAIL>(parts, C, st, DH, DXI, XO, G, mean, rstd, DX, DY, part, rows, seed,
+                                                          thresh16, inv_keep));
   } else {
-    NORM_DISPATCH(C, hipLaunchKernelGGL((add_norm_bwd_kernel<NS, WPR, false>), grid, dim3(64 * RowGroup<WPR>::kWaves), 0, st, DH, DXI, XO, G,
-                                        mean, rstd, DX, DY, part, rows, seed, thresh16, inv_keep));
+    NORM_DISPATCH(C, norm_bwd_launch<NS, WPR, false, TAIL>(parts, C, st, DH, DXI, XO, G, mean, rstd, DX, DY, part, rows, seed,
+                                                           thresh16, inv_keep));
   }
   return hipGetLastError();
 }

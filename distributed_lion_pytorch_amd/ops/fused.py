@@ -180,7 +180,8 @@ def _norm_parts(rows: int, C: int) -> int:
     # blocks of 4 waves, one fp32 partial row triple per block: enough waves to
     # cover the CUs a few times over while the partial stack stays a small
     # fraction of the row traffic (tools/bench_norm.py: 512 best at 20480x768).
-    # C <= 1024: 4 rows per block-iteration, wider: 1 (4-wave rows)
+    # C <= 1024 (exact or tail): 4 rows per block-iteration, wider: 1 (one
+    # ceil(C / 1024)-wave block per row) -- the NORM_DISPATCH rule
     rows_per_iter = _NORM_BWD_ROWS if C <= 1024 else 1
     return max(1, min(_NORM_PARTS_CAP, rows // (4 * rows_per_iter)))
 
@@ -320,13 +321,23 @@ class _Norm(torch.autograd.Function):
         return dx, dgamma, dbeta, None, None
 
 
-NORM_WIDTHS = (256, 512, 768, 1024, 2048, 3072, 4096, 5120, 6144, 8192)  # csrc/norm_kernels.hip NORM_DISPATCH
+# widths with an exact-width instantiation (compile-time C) in csrc/norm_kernels.hip NORM_DISPATCH
+NORM_WIDTHS = (256, 512, 768, 1024, 2048, 3072, 4096, 5120, 6144, 8192)
+
+
+def norm_supported(C: int) -> bool:
+    """Whether the fused add+norm kernels take rows of width C (bf16): any
+    256 <= C <= 8192 with C % 8 == 0.  NORM_WIDTHS run with C as a compile-time
+    constant; the rest run the tail-predicated form of the smallest capacity
+    that holds the row (one wave per row up to 1024, ceil(C / 1024) waves above)."""
+    return 256 <= C <= 8192 and C % 8 == 0
 
 
 def _norm_ok(x: torch.Tensor, gamma: torch.Tensor) -> bool:
     # the kernels hold a whole row in registers: one wave per row up to 1024,
-    # one 4-wave block per row for the Llama widths
-    return (x.dtype == torch.bfloat16 and gamma.dtype == torch.bfloat16 and x.shape[-1] in NORM_WIDTHS
+    # one block of ceil(C / 1024) waves per row above; narrower rows (the tiny
+    # test models) and widths off the 8-element grid take the ATen chain
+    return (x.dtype == torch.bfloat16 and gamma.dtype == torch.bfloat16 and norm_supported(x.shape[-1])
             and _use_hip(x))
 
 
