@@ -3,6 +3,7 @@ that uses the identical stateless dropout mask."""
 import pytest
 import torch
 
+import numerics as nm
 from distributed_lion_pytorch_amd.ops import fused, hip
 
 
@@ -67,6 +68,8 @@ def test_flash_attention_fwd_bwd(B, T, H, Hkv, D, p, cuda):
     _close(qs.grad, qr.grad, 3e-2)
     _close(ks.grad, kr.grad, 3e-2)
     _close(vs.grad, vr.grad, 3e-2)
+    nm.check_attention(f"fwd_bwd B={B} T={T} H={H}/{Hkv} D={D} p={p}", (out, qs.grad, ks.grad, vs.grad),
+                       q, k, v, dout, p, seed)
 
 
 @pytest.mark.gpu
@@ -85,6 +88,20 @@ def test_packed_qkv_attention_matches_reference(p, cuda):
     ref.backward(dout.float())
     _close(out, ref, 2e-2)
     _close(a.grad, r.grad, 3e-2)
+    nm.check_attention(f"packed T={T} H={H} D={D} p={p}", (out, a.grad[:, :, 0], a.grad[:, :, 1], a.grad[:, :, 2]),
+                       qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], dout, p, 99)
+
+
+def _check_bias_grad(got, x, w, b, dy, H):
+    """The c_attn bias gradient (column sums of dq | dk | dv from the kernels'
+    per-tile partials) elementwise against fp64, atol = tol x mean|ref|: the dk
+    third is zero in exact arithmetic (a softmax row's dS sums to zero) and
+    holds only the summed rounding of the dk values."""
+    B, T, C = x.shape
+    qkv = (x.detach().double() @ w.detach().double() + b.detach().double()).view(B, T, 3, H, C // H)
+    _, dq, dk, dv = nm.attention_ref64(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], dy, 0.0, 0, 0)
+    ref = torch.stack([dq, dk, dv]).sum((1, 2)).reshape(-1)
+    nm.assert_elems_close(got, ref, 3e-2, nm.vec_atol(ref, 3e-2), f"c_attn bias grad T={T}")
 
 
 @pytest.mark.parametrize("fuse", [False, True])
@@ -114,6 +131,7 @@ def test_qkv_attention_bias_grad_from_kernels(fuse, cuda):
     assert rel(y, yr) < 2e-2
     for got, ref in ((x.grad, xr.grad), (w.grad, wr.grad), (b.grad, br.grad)):
         assert rel(got, ref) < 3e-2, rel(got, ref)
+    _check_bias_grad(b.grad, x, w, b, dy, H)
 
 
 @pytest.mark.gpu
@@ -142,6 +160,8 @@ def test_flash_attention_tail_tiles(T, B, H, Hkv, D, p, cuda):
     _close(qs.grad, qr.grad, 3e-2, floor)
     _close(ks.grad, kr.grad, 3e-2, floor)
     _close(vs.grad, vr.grad, 3e-2)
+    nm.check_attention(f"tail T={T} B={B} H={H}/{Hkv} D={D} p={p}", (out, qs.grad, ks.grad, vs.grad),
+                       q, k, v, dout, p, 4321)
 
 
 @pytest.mark.gpu
@@ -174,6 +194,39 @@ def test_flash_attention_sliding_window(T, window, B, H, Hkv, p, cuda):
     _close(qs.grad, qr.grad, 3e-2, floor)
     _close(ks.grad, kr.grad, 3e-2, floor)
     _close(vs.grad, vr.grad, 3e-2)
+    nm.check_attention(f"window T={T} w={window} B={B} H={H}/{Hkv} p={p}", (out, qs.grad, ks.grad, vs.grad),
+                       q, k, v, dout, p, 77, window)
+
+
+# Dispatch corners of launch_attn_fwd / launch_attn_bwd (csrc/attention.hip) that
+# the tests above do not reach.  (H, Hkv, D, p, T)
+_KREG = [(2, 2, 128, 0.0, T) for T in (1, 33, 100, 129)]  # plain causal on the K-in-registers dK/dV kernel
+# the D = 64 forward takes two key tiles per barrier and every grid packs four
+# query tiles per block: odd tile counts, a last block with one live wave, a
+# one-row tail; with GQA, with and without dropout
+_TILES64 = [(4, 2, 64, p, T) for p in (0.0, 0.1) for T in (31, 32, 33, 65, 96, 97, 128, 129)]
+_DROP128 = [(4, 2, 128, 0.1, T) for T in (33, 100, 129)]  # D = 128 dropout without a window, with a tail
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("H,Hkv,D,p,T", _KREG + _TILES64 + _DROP128)
+def test_flash_attention_dispatch_corners(H, Hkv, D, p, T, cuda):
+    """Every row of out, dQ, dK and dV within C_ROWS x the bf16 rounding model of
+    the fp64 reference (tests/numerics.py), on the kernel / shape combinations
+    listed above."""
+    hip.require()
+    B = 2
+    torch.manual_seed(1000 * D + T)
+    q = torch.randn(B, T, H, D, device=cuda, dtype=torch.bfloat16)
+    k = torch.randn(B, T, Hkv, D, device=cuda, dtype=torch.bfloat16)
+    v = torch.randn(B, T, Hkv, D, device=cuda, dtype=torch.bfloat16)
+    dout = torch.randn(B, T, H * D, device=cuda, dtype=torch.bfloat16)
+    assert fused._attn_ok(q, T, D)
+    qs, ks, vs = (t.clone().requires_grad_() for t in (q, k, v))
+    out = fused._FlashAttn.apply(qs, ks, vs, p, 555).view(B, T, H * D)
+    out.backward(dout)
+    nm.check_attention(f"corner T={T} H={H}/{Hkv} D={D} p={p}", (out, qs.grad, ks.grad, vs.grad),
+                       q, k, v, dout, p, 555)
 
 
 @pytest.mark.gpu
@@ -232,6 +285,7 @@ def test_packed_qkv_bias_grad_tail_tile(cuda):
     assert rel(y, yr) < 2e-2
     for got, ref in ((x.grad, xr.grad), (w.grad, wr.grad), (b.grad, br.grad)):
         assert rel(got, ref) < 3e-2, rel(got, ref)
+    _check_bias_grad(b.grad, x, w, b, dy, H)
 
 
 def test_unsupported_head_dim_uses_math_sdpa_only(monkeypatch):

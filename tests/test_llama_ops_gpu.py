@@ -3,6 +3,7 @@ RMSNorm/LayerNorm (C = 2048..8192, multi-wave rows), SwiGLU and RoPE."""
 import pytest
 import torch
 
+import numerics as nm
 from distributed_lion_pytorch_amd.ops import fused, hip
 
 pytestmark = pytest.mark.gpu
@@ -194,6 +195,8 @@ def test_rope_attention_packed_grads(H, Hkv, T, fused_bwd, cuda, monkeypatch):
     assert rel(y, yr) < 2e-2
     for got, ref in ((gq, rq), (gk, rk), (gv, rv)):
         assert rel(got, ref) < 3e-2, rel(got, ref)
+    nm.check_attention(f"rope T={T} H={H}/{Hkv} fused_bwd={fused_bwd}", (y, gq, gk, gv),
+                       q.detach(), k.detach(), v.detach(), dy, 0.0, 0, 0, cos, sin)
 
 
 def test_swiglu_bwd_transposed_copy(cuda):

@@ -1,12 +1,39 @@
 """Fused softmax cross-entropy kernel (fp32-row, streaming and packed 16-bit
 row variants) vs an fp32 PyTorch reference: per-row loss and the in-place
 softmax - onehot."""
+import re
+
 import pytest
 import torch
 
+import numerics as nm
 from distributed_lion_pytorch_amd.ops import fused, hip
 
 pytestmark = pytest.mark.gpu
+
+# four half-ulps of the output type.  fp32: 256 ulps for the hardware exp2 and a
+# tree sum over V terms
+RTOL = {torch.bfloat16: 2.0 ** -7, torch.float16: 2.0 ** -9, torch.float32: 2.0 ** -16}
+ATOL = 2.0 ** -22  # one fp32 ulp of the p - 1 cancellation at the label
+
+
+def _check_xent64(x, y, loss, labels, V, name):
+    """y = softmax(x[:, :V]) - onehot (ignored rows and padded columns zero) and
+    the per-row loss against fp64, elementwise."""
+    N = x.shape[0]
+    rows = torch.arange(N, device=x.device)
+    valid = labels != -100
+    x64 = x[:, :V].double()
+    lse = torch.logsumexp(x64, -1)
+    ref_loss = (lse - x64[rows, labels.clamp_min(0)]) * valid
+    ref = torch.exp(x64 - lse[:, None])
+    ref[rows, labels.clamp_min(0)] -= 1
+    ref[~valid] = 0
+    assert loss.dtype == torch.float32 and y.dtype == x.dtype
+    nm.assert_elems_close(y[:, :V], ref, RTOL[x.dtype], ATOL, f"{name} softmax - onehot")
+    nm.assert_elems_close(loss, ref_loss, 1e-5, 1e-5, f"{name} loss")  # exact inputs, an fp32 loss
+    if x.shape[1] > V:
+        assert y[:, V:].abs().max().item() == 0.0
 
 
 # variant: 0 auto, 1 fp32 row in registers, 2 streaming, 4 / 5 packed row (512 / 1024 threads)
@@ -34,6 +61,56 @@ def test_softmax_xent_kernel(V, variant, cuda):
     assert (y[:, :V].float() - prob).abs().max().item() < 1e-2
     if Vp > V:
         assert y[:, V:].abs().max().item() == 0.0
+    _check_xent64(x, y, loss, labels, V, f"V={V} variant={variant}")
+
+
+def _kernels_run(fn):
+    """Names of the GPU kernels that fn() launches."""
+    from torch.profiler import ProfilerActivity, profile
+
+    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+        out = fn()
+        torch.cuda.synchronize()
+    names = [e.name for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA]
+    return out, names
+
+
+# fp32 rows have no packed kernel (variants 3..5 are 16-bit only): register-resident and streaming
+EDGE_CASES = ([(dt, V, var) for dt in (torch.bfloat16, torch.float16) for V in (100, 512, 50257)
+               for var in (0, 1, 2, 3, 4, 5)]
+              + [(torch.float32, V, var) for V in (100, 512, 50257) for var in (0, 2)])
+
+
+@pytest.mark.parametrize("dtype,V,variant", EDGE_CASES,
+                         ids=[f"{str(dt).split('.')[1]}-{V}-{var}" for dt, V, var in EDGE_CASES])
+def test_softmax_xent_dtypes_and_edge_rows(dtype, V, variant, cuda):
+    """Every instantiation of launch_softmax_xent (bf16 / fp16 / fp32, the
+    256-thread packed variant 3 included) on rows built to go wrong: labels 0,
+    V-1 and V-2 (for 50257 in the last partial group of 8 before the padding),
+    a label logit that dominates by 30 (p ~ 1: the stored gradient is a
+    cancellation), a 10 randn row (the max subtraction), ignored rows, and
+    V = 100 in 128 columns (most of a block's threads idle)."""
+    hip.require()
+    torch.manual_seed(V + variant)
+    N = 67
+    Vp = 128 if V == 100 else (V + 63) // 64 * 64
+    x = 2 * torch.randn(N, Vp, device=cuda)
+    labels = torch.randint(0, V, (N,), device=cuda)
+    labels[::7] = -100
+    labels[1], labels[2], labels[3] = 0, V - 1, V - 2
+    x[4, labels[4]] = x[4, :V].max() + 30
+    x[5] = 10 * torch.randn(Vp, device=cuda)
+    x = x.to(dtype)
+    y = x.clone()
+    run = lambda: hip.ops().softmax_xent_(y, labels, V, variant)  # noqa: E731
+    if variant == 3:
+        # launch_packed_dt: 256 threads hold at most 25 chunks of 8 per thread
+        assert (Vp + 2047) // 2048 <= 25
+        loss, names = _kernels_run(run)
+        assert any(re.search(r"softmax_xent_packed_kernel<\s*\d+,\s*256,", n) for n in names), names
+    else:
+        loss = run()
+    _check_xent64(x, y, loss, labels, V, f"{dtype} V={V} variant={variant}")
 
 
 def test_lm_head_ce_wide_vocab_matches_reference(cuda):
@@ -49,6 +126,13 @@ def test_lm_head_ce_wide_vocab_matches_reference(cuda):
     loss.backward()
     ref.backward()
     assert (h.grad.float() - hr.grad).abs().max().item() < 2e-2 * hr.grad.abs().max().item() + 1e-4
+    # per token row against fp64; the rounding model is the fp64 gradient rounded to bf16
+    h64, w64 = h.detach().double(), w.detach().double()
+    logits = (h64 @ w64.t()).view(-1, 128256)
+    g = torch.softmax(logits, -1)
+    g[torch.arange(g.shape[0], device=cuda), labels.view(-1)] -= 1
+    ref64 = ((g / g.shape[0]) @ w64).view_as(h)
+    nm.assert_rows_close(h.grad, ref64, ref64.bfloat16(), nm.C_ROWS, None, "lm_head h.grad")
 
 
 def test_lm_head_ce_parameter_uses_own_dgrad_gemm(cuda):
