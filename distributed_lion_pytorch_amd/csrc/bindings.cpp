@@ -110,7 +110,15 @@ void lion_vote_apply(const Tensor& meta, int64_t seg_off, int64_t chunk_off, int
   check_dev(alive, "alive");
   TORCH_CHECK(planes.scalar_type() == at::kByte, "dlion: planes must be uint8");
   TORCH_CHECK(alive.scalar_type() == at::kByte, "dlion: alive must be uint8");
-  TORCH_CHECK(mode >= 0 && mode <= 2, "dlion: bad vote mode ", mode);
+  TORCH_CHECK(mode >= 0 && mode <= 3, "dlion: bad vote mode ", mode);
+  if (mode == 3) {  // counted: planes is [W][P][shard], plane_stride the shard bytes
+    const int64_t w = alive.numel();
+    TORCH_CHECK(w >= 1 && w <= 15, "dlion: counted apply needs 1 <= W <= 15, got ", w);
+    int64_t p = 0;
+    while (w >> p) ++p;
+    TORCH_CHECK(plane_stride > 0 && plane_stride % 256 == 0, "dlion: counted apply shard bytes must be a multiple of 256");
+    TORCH_CHECK(planes.numel() >= w * p * plane_stride, "dlion: counted apply count planes too small");
+  }
   const uint8_t* negp = nullptr;
   if (neg.has_value()) {
     check_dev(*neg, "neg");
@@ -162,6 +170,33 @@ void vote_reduce(const Tensor& recv, int64_t nbytes, const Tensor& alive, int64_
                                       static_cast<int>(alive.numel()), static_cast<int>(tie),
                                       out.data_ptr<uint8_t>(), negp, tp, cur_stream()),
             "vote_reduce");
+}
+
+// out[P][nbytes]: bit planes of each coordinate's live-voter count, P = bit_length(W)
+void vote_count(const Tensor& recv, int64_t nbytes, const Tensor& alive, const Tensor& out,
+                const std::optional<Tensor>& ties) {
+  check_dev(recv, "recv");
+  check_dev(alive, "alive");
+  check_dev(out, "out");
+  TORCH_CHECK(recv.scalar_type() == at::kByte && out.scalar_type() == at::kByte && alive.scalar_type() == at::kByte,
+              "dlion: vote_count buffers must be uint8");
+  const int64_t w = alive.numel();
+  TORCH_CHECK(w >= 1 && w <= 15, "dlion: vote_count needs 1 <= W <= 15, got ", w);
+  int64_t p = 0;
+  while (w >> p) ++p;
+  TORCH_CHECK(nbytes >= 0 && nbytes % 4 == 0, "dlion: vote_count shard bytes must be a multiple of 4");
+  TORCH_CHECK(out.numel() >= p * nbytes, "dlion: vote_count out too small");
+  TORCH_CHECK(recv.numel() >= nbytes * w, "dlion: vote_count recv too small");
+  unsigned long long* tp = nullptr;
+  if (ties.has_value()) {
+    check_dev(*ties, "ties");
+    TORCH_CHECK(ties->scalar_type() == at::kLong && ties->numel() >= 1, "dlion: ties must be int64");
+    tp = reinterpret_cast<unsigned long long*>(ties->data_ptr<int64_t>());
+  }
+  const c10::DeviceGuard g(recv.device());
+  check_hip(dlion::launch_vote_count(recv.data_ptr<uint8_t>(), nbytes, alive.data_ptr<uint8_t>(),
+                                     static_cast<int>(w), out.data_ptr<uint8_t>(), tp, cur_stream()),
+            "vote_count");
 }
 
 int dtype_code(at::ScalarType t) {
@@ -1215,6 +1250,7 @@ TORCH_LIBRARY(dlion, m) {
       " Tensor? own, Tensor(b!)? agree) -> ()");
   m.def("vote_reduce(Tensor recv, int nbytes, Tensor alive, int tie, Tensor(a!) out, Tensor(b!)? neg_out,"
         " Tensor(c!)? ties=None) -> ()");
+  m.def("vote_count(Tensor recv, int nbytes, Tensor alive, Tensor(a!) out, Tensor(b!)? ties) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(dlion, CUDA, m) {
@@ -1222,6 +1258,7 @@ TORCH_LIBRARY_IMPL(dlion, CUDA, m) {
   m.impl("lion_encode", &lion_encode);
   m.impl("lion_vote_apply", &lion_vote_apply);
   m.impl("vote_reduce", &vote_reduce);
+  m.impl("vote_count", &vote_count);
   m.impl("grad_sumsq", &grad_sumsq);
   m.impl("clip_coef", &clip_coef);
   m.impl("softmax_xent_", &softmax_xent_);

@@ -12,6 +12,8 @@
 //   K2 lion_vote_apply p, W bit planes -> p   popcount majority / average vote
 //                                             + decoupled WD + step (ref :84-92)
 //   K4 vote_reduce     W shards -> voted bits  (all-to-all "vote-RS" scheme)
+//   K4c vote_count     W shards -> count bit planes (average vote on the
+//                                             all-to-all path; K2 mode 3 applies them)
 //
 // Multi-tensor layout (built once per parameter set by parallel/plan.py):
 //   seg   [T][8] int64 : p_ptr, g_ptr, m_ptr, numel, bit_off, flags, 0, 0
@@ -286,6 +288,8 @@ lion_encode_kernel(const int64_t* __restrict__ seg, const int64_t* __restrict__ 
 // mode 1: average (paper's server "Averaging")  delta = (2c - n) / n
 // mode 2: pre-voted bitmap (vote-RS/AG path)    delta = pos ? +1 : (neg ? -1 : 0)
 //         planes = pos bitmap, neg = optional neg bitmap (nullptr -> ~pos)
+// mode 3: counted (average on the a2a path)     delta = (2c - n) / n, c read from
+//         the gathered count planes (lion_apply_counted_kernel below)
 // tie: 0 -> -1 (reference parity: torch.mode tie -> False), 1 -> 0, 2 -> +1
 // p <- round(round(p * decay) - lr * delta)   (ref :64 then :92)
 // agree (optional): count of coordinates where this rank's own bits (`own`,
@@ -375,13 +379,13 @@ lion_vote_apply_kernel(const int64_t* __restrict__ seg, const int64_t* __restric
 // and pre-voted bitmaps (mode 2); mode 1 and wider worlds use the byte kernel.
 constexpr int kMaxSliced = 15;
 
-// Majority over up to 15 planes for 32 coordinates at once: a 4-bit vertical
-// counter per bit position (7 bitwise ops per plane), then count vs
-// K = floor(n_live / 2) compared bit-sliced from the MSB.  pos / neg follow the
-// byte kernels' rules (ties by `tie`, nobody alive -> neither).
-__device__ __forceinline__ void sliced_vote(const uint32_t (&w)[kMaxSliced], int world, int n_live, int tie,
-                                            uint32_t& pos, uint32_t& neg, uint32_t& ties) {
-  uint32_t c0 = 0, c1 = 0, c2 = 0, c3 = 0;
+// The 4-bit vertical counter over up to 15 (masked) plane words: bit i of
+// c0..c3 is bit 0..3 of the number of planes whose bit i is set (7 bitwise
+// ops per plane for 32 coordinates).  Shared by the majority vote below and
+// the count planes of the average vote (K4c).
+__device__ __forceinline__ void sliced_count(const uint32_t (&w)[kMaxSliced], int world, uint32_t& c0, uint32_t& c1,
+                                             uint32_t& c2, uint32_t& c3) {
+  c0 = c1 = c2 = c3 = 0;
 #pragma unroll
   for (int k = 0; k < kMaxSliced; ++k) {
     if (k >= world) break;  // uniform
@@ -394,6 +398,16 @@ __device__ __forceinline__ void sliced_vote(const uint32_t (&w)[kMaxSliced], int
     c2 ^= t1;
     c3 ^= t2;
   }
+}
+
+// Majority over up to 15 planes for 32 coordinates at once: the vertical
+// counter, then count vs K = floor(n_live / 2) compared bit-sliced from the
+// MSB.  pos / neg follow the byte kernels' rules (ties by `tie`, nobody alive
+// -> neither).
+__device__ __forceinline__ void sliced_vote(const uint32_t (&w)[kMaxSliced], int world, int n_live, int tie,
+                                            uint32_t& pos, uint32_t& neg, uint32_t& ties) {
+  uint32_t c0, c1, c2, c3;
+  sliced_count(w, world, c0, c1, c2, c3);
   const int K = n_live >> 1;
   uint32_t gt = 0, eq = 0xffffffffu;
   const uint32_t cb[4] = {c0, c1, c2, c3};
@@ -657,6 +671,194 @@ lion_apply_pair_kernel(const int64_t* __restrict__ seg, const int64_t* __restric
     if (has[c]) apply_chunk<DT, MAJ>(rs[c], st[c], v, decay, neg_lr);
 }
 
+// ------------------------------------------------------- K2, counted (mode 3)
+// The average vote on the a2a path.  K4c (below) wrote each coordinate's
+// live-voter count as P = bit_length(W) bit planes per shard, and the
+// all-gather laid the ranks' blocks out as planes[W][P][shard]: for the
+// bucket-relative byte x, with r = x / shard and o = x % shard, bit j of the
+// counts of its 8 coordinates is the byte planes[(r * P + j) * shard + o].
+// shard % 256 == 0 (the planner pads buckets to 256 * W) and one block
+// iteration covers a 256-byte-aligned span of 2048 coordinates, so r is
+// uniform over the block in each iteration: one division per chunk, then a
+// step per iteration -- never hoisted over a chunk, whose 1024 bytes may
+// straddle shards.  The arithmetic is the byte kernel's mode 1,
+// delta = float(2c - n_live) * (1 / n_live), so the results are bit-identical.
+constexpr int kMaxCountPlanes = 4;  // bit_length(kMaxSliced)
+
+__host__ __device__ inline int count_plane_bits(int world) {
+  int p = 0;
+  while (world >> p) ++p;
+  return p;
+}
+
+struct CountCtx {
+  const uint8_t* planes;
+  int64_t shard;
+  int P, n_live;
+  float inv_n;
+};
+
+struct SpanPos {
+  int64_t r, o;  // shard index, byte offset inside the shard (both block-uniform)
+};
+
+__device__ __forceinline__ SpanPos span_pos(int64_t byte, int64_t shard) {
+  // the chunk's first byte comes from the metadata tables: the same in every lane
+  const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(byte));
+  const uint32_t hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(static_cast<uint64_t>(byte) >> 32));
+  SpanPos s;
+  if (hi == 0 && (shard >> 32) == 0) {
+    const uint32_t q = lo / static_cast<uint32_t>(shard);
+    s.r = q;
+    s.o = lo - q * static_cast<uint32_t>(shard);
+  } else {
+    const int64_t x = static_cast<int64_t>((static_cast<uint64_t>(hi) << 32) | lo);
+    s.r = x / shard;
+    s.o = x - s.r * shard;
+  }
+  return s;
+}
+
+__device__ __forceinline__ void next_span(SpanPos& s, int64_t shard) {
+  s.o += kSpan / 8;
+  if (s.o >= shard) {  // o and shard are multiples of 256: o == shard exactly
+    s.o = 0;
+    ++s.r;
+  }
+}
+
+// the lane's dword of every count plane (the 4 lanes of a quad share it)
+__device__ __forceinline__ void load_counts(const CountCtx& v, const SpanPos& s, uint32_t (&cw)[kMaxCountPlanes]) {
+  const uint8_t* base = v.planes + s.r * v.P * v.shard + s.o + (threadIdx.x & ~3u);
+#pragma unroll
+  for (int j = 0; j < kMaxCountPlanes; ++j)
+    cw[j] = j < v.P ? *reinterpret_cast<const uint32_t*>(base + j * v.shard) : 0u;  // uniform
+}
+
+// delta of the lane's 8 coordinates from its byte of each count plane.  With
+// m = [b0 b1 b2 b3] (byte j = plane j), the bits of coordinate k sit at
+// 8j + k; for k = r and r + 4, G = (m >> r) & 0x11111111 keeps them at 8j and
+// 8j + 4, and two shift-ors fold the four planes into the low byte:
+// nibble 0 = count of coordinate r, nibble 1 = count of coordinate r + 4.
+__device__ __forceinline__ void counted_delta8(const uint32_t (&cw)[kMaxCountPlanes], const CountCtx& v,
+                                               float (&delta)[8]) {
+  const int sh = 8 * (threadIdx.x & 3);
+  const uint32_t m = ((cw[0] >> sh) & 0xffu) | (((cw[1] >> sh) & 0xffu) << 8) | (((cw[2] >> sh) & 0xffu) << 16) |
+                     (((cw[3] >> sh) & 0xffu) << 24);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const uint32_t g = (m >> r) & 0x11111111u;
+    const uint32_t u = g | (g >> 7);
+    const uint32_t w = u | (u >> 14);
+    const int ca = static_cast<int>(w & 0xfu), cb = static_cast<int>((w >> 4) & 0xfu);
+    delta[r] = static_cast<float>(2 * ca - v.n_live) * v.inv_n;
+    delta[r + 4] = static_cast<float>(2 * cb - v.n_live) * v.inv_n;
+  }
+}
+
+template <int DT>
+__device__ __forceinline__ void apply8_delta(float (&pv)[8], const float (&delta)[8], float decay, float neg_lr) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) pv[j] = __fmaf_rn(neg_lr, delta[j], Elem<DT>::rnd(pv[j] * decay));
+}
+
+template <int DT, bool TEL>
+__device__ __forceinline__ void counted_chunk(const SegRow& r, int64_t start, const CountCtx& v, float decay,
+                                              float neg_lr, const uint8_t* __restrict__ own, uint32_t& n_agree) {
+  using S = typename Elem<DT>::S;
+  S* p = const_cast<S*>(static_cast<const S*>(r.p));
+  SpanPos sp = span_pos((r.bit_off + start) >> 3, v.shard);
+#pragma unroll
+  for (int it = 0; it < kIters; ++it) {
+    if (it > 0) next_span(sp, v.shard);
+    const int64_t e = start + it * kSpan + threadIdx.x * 8;
+    if (e >= r.n) break;
+    uint32_t cw[kMaxCountPlanes];
+    load_counts(v, sp, cw);
+    float delta[8], pv[8];
+    counted_delta8(cw, v, delta);
+    if constexpr (TEL) {
+      const uint32_t mine = own[(r.bit_off + e) >> 3];
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (e + j < r.n) n_agree += (((mine >> j) & 1) ? 1.f : -1.f) * delta[j] > 0.f;
+    }
+    load8g<DT>(p, e, r.n, r.vec, pv);
+    apply8_delta<DT>(pv, delta, decay, neg_lr);
+    store8g<DT>(p, e, r.n, r.vec, pv);
+  }
+}
+
+// Without telemetry: CPB = kPairChunks chunks per block, as in
+// lion_apply_pair_kernel; when every chunk is full all p vectors and all P
+// plane words (at most 8 x 4 dwords + 8 Raw8) are loaded before the first use.
+// With telemetry (TEL, CPB = 1): agree[0] += #(own sign * delta > 0); the ties
+// were counted by K4c on the shard, as in the pre-voted path.
+template <int DT, int CPB, bool TEL>
+__global__ void __launch_bounds__(kThreads)
+lion_apply_counted_kernel(const int64_t* __restrict__ seg, const int64_t* __restrict__ chunks, int64_t n_chunks,
+                          const uint8_t* __restrict__ planes, int64_t shard, const uint8_t* __restrict__ alive,
+                          int world, float decay, float neg_lr, const uint8_t* __restrict__ own,
+                          unsigned long long* __restrict__ agree) {
+  using E = Elem<DT>;
+  using S = typename E::S;
+  const int64_t c0 = CPB * static_cast<int64_t>(blockIdx.x);
+  int64_t sidx[CPB], st[CPB];
+  bool has[CPB];
+#pragma unroll
+  for (int c = 0; c < CPB; ++c) {
+    has[c] = c0 + c < n_chunks;  // chunk 0 always exists
+    const int64_t ci = has[c] ? c0 + c : c0;
+    sidx[c] = chunks[2 * ci];
+    st[c] = chunks[2 * ci + 1];
+  }
+  SegRow rs[CPB];
+#pragma unroll
+  for (int c = 0; c < CPB; ++c) rs[c] = load_seg(seg, sidx[c]);
+  CountCtx v{planes, shard, count_plane_bits(world), 0, 0.f};
+  for (int k = 0; k < world; ++k) v.n_live += alive[k] != 0;
+  v.inv_n = v.n_live > 0 ? 1.f / static_cast<float>(v.n_live) : 0.f;  // nobody voted: counts 0, delta 0
+  if constexpr (!TEL) {
+    bool full = true;
+#pragma unroll
+    for (int c = 0; c < CPB; ++c) full = full && has[c] && rs[c].vec && st[c] + kChunk <= rs[c].n;
+    if (full) {  // block-uniform
+      Raw8<DT> rp[CPB * kIters];
+      uint32_t cw[CPB * kIters][kMaxCountPlanes];
+      SpanPos sp{0, 0};
+#pragma unroll
+      for (int q = 0; q < CPB * kIters; ++q) {
+        const int c = q / kIters;
+        if (q % kIters == 0)
+          sp = span_pos((rs[c].bit_off + st[c]) >> 3, shard);
+        else
+          next_span(sp, shard);
+        rp[q].load(static_cast<const S*>(rs[c].p) + st[c] + (q % kIters) * kSpan + threadIdx.x * 8);
+        load_counts(v, sp, cw[q]);
+      }
+#pragma unroll
+      for (int q = 0; q < CPB * kIters; ++q) {
+        const int c = q / kIters;
+        const int64_t e = st[c] + (q % kIters) * kSpan + threadIdx.x * 8;
+        float delta[8], pv[8];
+        counted_delta8(cw[q], v, delta);
+        rp[q].unpack(pv);
+        apply8_delta<DT>(pv, delta, decay, neg_lr);
+        E::store8(const_cast<S*>(static_cast<const S*>(rs[c].p)) + e, pv);
+      }
+      return;
+    }
+  }
+  uint32_t n_agree = 0;
+#pragma unroll
+  for (int c = 0; c < CPB; ++c)
+    if (has[c]) counted_chunk<DT, TEL>(rs[c], st[c], v, decay, neg_lr, own, n_agree);
+  if constexpr (TEL) {
+    for (int off = 32; off > 0; off >>= 1) n_agree += __shfl_xor(n_agree, off);
+    if ((threadIdx.x & 63) == 0) atomicAdd(agree, static_cast<unsigned long long>(n_agree));
+  }
+}
+
 // ----------------------------------------------------------------------- K4
 // recv: [W][nbytes] shards gathered by all_to_all; out: voted positive bits;
 // neg_out (optional): voted negative bits (only needed when ties map to 0).
@@ -745,6 +947,73 @@ vote_reduce_kernel(const uint8_t* __restrict__ recv, int64_t nbytes, const uint8
       reinterpret_cast<uint32_t*>(out)[w] = pos;
       if (neg_out != nullptr) reinterpret_cast<uint32_t*>(neg_out)[w] = ng;
     }
+  }
+  if (ties != nullptr) {
+    for (int off = 32; off > 0; off >>= 1) n_tie += __shfl_xor(n_tie, off);
+    if ((threadIdx.x & 63) == 0 && n_tie) atomicAdd(ties, static_cast<unsigned long long>(n_tie));
+  }
+}
+
+// ---------------------------------------------------------------------- K4c
+// The shard vote of the average rule: recv is [W][nbytes] as for K4, out is
+// [P][nbytes] with P = bit_length(W); plane j holds bit j of each coordinate's
+// live-voter count (dead planes masked, as in K4).  Launch shape of the sliced
+// K4: 32 coordinates per thread, two words per grid-stride step with every
+// plane load issued first.  ties (optional) += #(2c == n_live, n_live > 0).
+__device__ __forceinline__ uint32_t count_tie_bits(const uint32_t (&c)[kMaxCountPlanes], int n_live) {
+  if (n_live == 0 || (n_live & 1)) return 0u;
+  const int K = n_live >> 1;
+  uint32_t eq = 0xffffffffu;
+#pragma unroll
+  for (int b = 0; b < kMaxCountPlanes; ++b) eq &= ((K >> b) & 1) ? c[b] : ~c[b];
+  return eq;
+}
+
+__global__ void __launch_bounds__(kThreads)
+vote_count_kernel(const uint8_t* __restrict__ recv, int64_t nbytes, const uint8_t* __restrict__ alive, int world,
+                  uint8_t* __restrict__ out, unsigned long long* __restrict__ ties) {
+  const int64_t nwords = nbytes >> 2;  // nbytes % 4 == 0 (checked by the caller)
+  const int P = count_plane_bits(world);
+  int n_live = 0;
+  uint32_t live_mask = 0;
+  for (int k = 0; k < world; ++k) {
+    live_mask |= static_cast<uint32_t>(alive[k] != 0) << k;
+    n_live += alive[k] != 0;
+  }
+  uint32_t* __restrict__ o32 = reinterpret_cast<uint32_t*>(out);
+  uint32_t n_tie = 0;
+  const int64_t stride = (int64_t)gridDim.x * kThreads;
+  int64_t w = blockIdx.x * (int64_t)kThreads + threadIdx.x;
+  for (; w + stride < nwords; w += 2 * stride) {
+    uint32_t v[kMaxSliced], u[kMaxSliced];
+#pragma unroll
+    for (int k = 0; k < kMaxSliced; ++k) {
+      const bool on = (live_mask >> k) & 1;
+      v[k] = on ? reinterpret_cast<const uint32_t*>(recv + k * nbytes)[w] : 0u;
+      u[k] = on ? reinterpret_cast<const uint32_t*>(recv + k * nbytes)[w + stride] : 0u;
+    }
+    uint32_t c[kMaxCountPlanes], d[kMaxCountPlanes];
+    sliced_count(v, world, c[0], c[1], c[2], c[3]);
+    sliced_count(u, world, d[0], d[1], d[2], d[3]);
+    n_tie += __popc(count_tie_bits(c, n_live)) + __popc(count_tie_bits(d, n_live));
+#pragma unroll
+    for (int j = 0; j < kMaxCountPlanes; ++j)
+      if (j < P) {  // uniform
+        o32[j * nwords + w] = c[j];
+        o32[j * nwords + w + stride] = d[j];
+      }
+  }
+  for (; w < nwords; w += stride) {
+    uint32_t v[kMaxSliced];
+#pragma unroll
+    for (int k = 0; k < kMaxSliced; ++k)
+      v[k] = (live_mask >> k) & 1 ? reinterpret_cast<const uint32_t*>(recv + k * nbytes)[w] : 0u;
+    uint32_t c[kMaxCountPlanes];
+    sliced_count(v, world, c[0], c[1], c[2], c[3]);
+    n_tie += __popc(count_tie_bits(c, n_live));
+#pragma unroll
+    for (int j = 0; j < kMaxCountPlanes; ++j)
+      if (j < P) o32[j * nwords + w] = c[j];
   }
   if (ties != nullptr) {
     for (int off = 32; off > 0; off >>= 1) n_tie += __shfl_xor(n_tie, off);
@@ -857,6 +1126,21 @@ hipError_t launch_lion_vote_apply(int dt, const int64_t* seg, const int64_t* chu
                                   int mode, int tie, const uint8_t* neg, float decay, float neg_lr,
                                   const uint8_t* own, unsigned long long* agree, hipStream_t st) {
   if (n_chunks == 0) return hipSuccess;
+  if (mode == 3) {  // counted: planes[W][P][shard], plane_stride = shard
+    if (world < 1 || world > kMaxSliced || plane_stride <= 0 || plane_stride % (kSpan / 8) != 0)
+      return hipErrorInvalidValue;
+    if (agree == nullptr) {
+      DLION_DISPATCH(dt, hipLaunchKernelGGL((lion_apply_counted_kernel<DT, kPairChunks, false>),
+                                            dim3((n_chunks + kPairChunks - 1) / kPairChunks), dim3(kThreads), 0, st, seg,
+                                            chunks, n_chunks, planes, plane_stride, alive, world, decay, neg_lr, own,
+                                            agree));
+    } else {
+      DLION_DISPATCH(dt, hipLaunchKernelGGL((lion_apply_counted_kernel<DT, 1, true>), dim3(n_chunks), dim3(kThreads), 0,
+                                            st, seg, chunks, n_chunks, planes, plane_stride, alive, world, decay, neg_lr,
+                                            own, agree));
+    }
+    return hipGetLastError();
+  }
   if (mode == 2 && agree == nullptr) {
     DLION_DISPATCH(dt, hipLaunchKernelGGL((lion_apply_pair_kernel<DT, false, kPairChunks>), dim3((n_chunks + kPairChunks - 1) / kPairChunks),
                                           dim3(kThreads), 0, st, seg, chunks, n_chunks, planes, plane_stride, alive,
@@ -907,6 +1191,18 @@ hipError_t launch_vote_reduce(const uint8_t* recv, int64_t nbytes, const uint8_t
   else
     hipLaunchKernelGGL(vote_reduce_kernel<false>, dim3(blocks), dim3(kThreads), 0, st, recv, nbytes, alive, world,
                        tie, out, neg_out, ties);
+  return hipGetLastError();
+}
+
+hipError_t launch_vote_count(const uint8_t* recv, int64_t nbytes, const uint8_t* alive, int world, uint8_t* out,
+                             unsigned long long* ties, hipStream_t st) {
+  if (world < 1 || world > kMaxSliced) return hipErrorInvalidValue;
+  const int64_t nwords = nbytes >> 2;
+  if (nwords == 0) return hipSuccess;
+  const int64_t per_block = static_cast<int64_t>(kThreads) * kK4Unroll;
+  int64_t blocks = (nwords + per_block - 1) / per_block;
+  if (blocks > kK4MaxBlocks) blocks = kK4MaxBlocks;
+  hipLaunchKernelGGL(vote_count_kernel, dim3(blocks), dim3(kThreads), 0, st, recv, nbytes, alive, world, out, ties);
   return hipGetLastError();
 }
 

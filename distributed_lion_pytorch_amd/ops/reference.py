@@ -33,6 +33,7 @@ TIE_CODES = {"negative": TIE_NEGATIVE, "ref_negative": TIE_NEGATIVE, "zero": TIE
 VOTE_MAJORITY = 0
 VOTE_AVERAGE = 1
 VOTE_PREVOTED = 2
+VOTE_COUNTED = 3  # average from the gathered count bit planes (a2a path)
 VOTE_CODES = {"majority": VOTE_MAJORITY, "average": VOTE_AVERAGE}
 
 
@@ -144,13 +145,42 @@ def vote_delta(planes_bits: torch.Tensor, alive: torch.Tensor, mode: int = VOTE_
     cnt = planes_bits[alive_b].to(torch.int32).sum(0)
     twice = 2 * cnt
     if mode == VOTE_AVERAGE:
-        inv = torch.tensor(1.0 / n_live, dtype=torch.float32).item()
-        return (twice - n_live).to(torch.float32) * inv
+        return _average_delta(cnt, n_live)
     tie_val = {TIE_NEGATIVE: -1.0, TIE_ZERO: 0.0, TIE_POSITIVE: 1.0}[tie]
     d = torch.full(cnt.shape, tie_val, dtype=torch.float32, device=cnt.device)
     d[twice > n_live] = 1.0
     d[twice < n_live] = -1.0
     return d
+
+
+def _average_delta(cnt: torch.Tensor, n_live: int) -> torch.Tensor:
+    """(2c - n_live) * fp32(1 / n_live): the kernels' expression for the average."""
+    inv = torch.tensor(1.0 / n_live, dtype=torch.float32).item()
+    return (2 * cnt - n_live).to(torch.float32) * inv
+
+
+def count_plane_bits(world: int) -> int:
+    """P: bit planes that hold a live-voter count of up to ``world``."""
+    return int(world).bit_length()
+
+
+def count_planes(planes_bits: torch.Tensor, alive: torch.Tensor, world: int) -> torch.Tensor:
+    """bool[W, n] -> bool[P, n]: plane j is bit j of each coordinate's count of
+    live voters (the K4c oracle), P = ``world.bit_length()``."""
+    alive_b = alive.to(torch.bool)
+    cnt = planes_bits[alive_b].to(torch.int32).sum(0)
+    shifts = torch.arange(count_plane_bits(world), dtype=torch.int32, device=cnt.device)
+    return ((cnt.unsqueeze(0) >> shifts.unsqueeze(1)) & 1).bool()
+
+
+def counted_delta(count_bits: torch.Tensor, n_live: int) -> torch.Tensor:
+    """bool[P, n] count planes -> float32 delta[n] of the average vote; the
+    same expression as ``vote_delta``'s average branch, no voters -> 0."""
+    if n_live == 0:
+        return torch.zeros(count_bits.shape[1], dtype=torch.float32, device=count_bits.device)
+    shifts = torch.arange(count_bits.shape[0], dtype=torch.int32, device=count_bits.device)
+    cnt = (count_bits.to(torch.int32) << shifts.unsqueeze(1)).sum(0).to(torch.int32)
+    return _average_delta(cnt, n_live)
 
 
 def prevoted_delta(pos_bits: torch.Tensor, neg_bits: Optional[torch.Tensor]) -> torch.Tensor:

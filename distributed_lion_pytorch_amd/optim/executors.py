@@ -72,6 +72,11 @@ class HipExecutor:
                     neg_out: Optional[torch.Tensor], ties: Optional[torch.Tensor] = None) -> None:
         self.ops.vote_reduce(recv, nbytes, alive, tie, out, neg_out, ties)
 
+    def vote_count(self, recv: torch.Tensor, nbytes: int, alive: torch.Tensor, out: torch.Tensor,
+                   ties: Optional[torch.Tensor] = None) -> None:
+        """out[P][nbytes]: bit planes of each coordinate's live-voter count (K4c)."""
+        self.ops.vote_count(recv, nbytes, alive, out, ties)
+
 
 class TorchExecutor:
     name = "torch"
@@ -109,11 +114,20 @@ class TorchExecutor:
     def apply(self, meta, b: Bucket, planes: torch.Tensor, stride: int, alive: torch.Tensor, mode: int, tie: int,
               neg: Optional[torch.Tensor], hp: HParams, own: Optional[torch.Tensor] = None,
               agree: Optional[torch.Tensor] = None) -> None:
-        w = planes.numel() // stride if mode != ref.VOTE_PREVOTED else 1
-        pl = planes.reshape(w, stride)
+        if mode == ref.VOTE_COUNTED:
+            # [W][P][shard] (stride = shard bytes) -> P count planes in bucket byte order
+            w = alive.numel()
+            npl = ref.count_plane_bits(w)
+            pl = planes[: w * npl * stride].reshape(w, npl, stride).permute(1, 0, 2).reshape(npl, w * stride)
+            n_live = int(alive.to(torch.bool).sum())
+        else:
+            w = planes.numel() // stride if mode != ref.VOTE_PREVOTED else 1
+            pl = planes.reshape(w, stride)
         for s in b.segments:
             o, nb = s.bit_off // 8, _region_bytes(s.numel)
-            if mode == ref.VOTE_PREVOTED:
+            if mode == ref.VOTE_COUNTED:
+                delta = ref.counted_delta(ref.unpack_bits(pl[:, o:o + nb], s.numel), n_live)
+            elif mode == ref.VOTE_PREVOTED:
                 pos = ref.unpack_bits(pl[0, o:o + nb], s.numel)
                 ngb = None if neg is None else ref.unpack_bits(neg[o:o + nb], s.numel)
                 delta = ref.prevoted_delta(pos, ngb)
@@ -123,7 +137,7 @@ class TorchExecutor:
             if agree is not None and own is not None:
                 mine = ref.unpack_bits(own[o:o + nb], s.numel)
                 agree[0] += ((mine.float() * 2 - 1) * delta > 0).sum().to(agree.dtype)
-                if mode != ref.VOTE_PREVOTED:  # pre-voted planes: K4 counted the ties
+                if mode not in (ref.VOTE_PREVOTED, ref.VOTE_COUNTED):  # a2a paths: K4 / K4c counted the ties
                     live = alive.to(torch.bool)
                     twice = 2 * bits[live].to(torch.int64).sum(0)
                     agree[1] += ((twice == int(live.sum())) & (int(live.sum()) > 0)).sum().to(agree.dtype)
@@ -142,6 +156,19 @@ class TorchExecutor:
         out[:nbytes] = ref.pack_bits(pos)
         if neg_out is not None:
             neg_out[:nbytes] = ref.pack_bits(ngb)
+
+    def vote_count(self, recv: torch.Tensor, nbytes: int, alive: torch.Tensor, out: torch.Tensor,
+                   ties: Optional[torch.Tensor] = None) -> None:
+        w = alive.numel()
+        bits = ref.unpack_bits(recv[: w * nbytes].view(w, nbytes))
+        cb = ref.count_planes(bits, alive, w)
+        if ties is not None:
+            live = alive.to(torch.bool)
+            n_live = int(live.sum())
+            twice = 2 * bits[live].to(torch.int64).sum(0)
+            ties += ((twice == n_live) & (n_live > 0)).sum().to(ties.dtype)
+        for j in range(cb.shape[0]):
+            out[j * nbytes:(j + 1) * nbytes] = ref.pack_bits(cb[j])
 
 
 def make_executor(plan: FlatPlan, backend: str = "auto"):

@@ -16,7 +16,9 @@ update semantics, but a different execution model:
   defects D2-D5 of the reference are fixed.
 
 Keyword-only extensions (all optional):
-  vote         "majority" (reference) | "average" (paper's server averaging)
+  vote         "majority" (reference) | "average" (paper's server averaging;
+               with exchange="a2a" it travels as count bit planes at
+               5 <= W <= 15 and over the all-gather otherwise)
   tie_break    "negative" (reference parity) | "zero" | "positive"
   exchange     vote exchange strategy, see parallel/exchange.py
   bucket_mb    packed-bit bucket size (MB) -- one collective per bucket.  None
@@ -121,6 +123,9 @@ class Lion(Optimizer):
         # run the vote path (encode -> collectives -> apply) even on a 1-rank
         # group: exercises the RCCL calls on a single GPU (tests/test_nccl_gpu.py)
         self._force_vote = False
+        # route a2a + average over the count planes at any W <= 15 (by default
+        # only where they move fewer bytes than the all-gather, W >= 5)
+        self._force_counts = False
         self._wire_carry = WireCounter()  # counts of exchanges replaced after a regroup
 
     # ------------------------------------------------------------ topology
@@ -211,10 +216,13 @@ class Lion(Optimizer):
                 self._check_consistency(plan)
             self._exchange = make_exchange(self.exchange_name, plan, self.process_group, rank, world,
                                            self._executor, ref.TIE_CODES[self.tie_break],
-                                           ref.VOTE_CODES[self.vote])
+                                           ref.VOTE_CODES[self.vote], counts=self._counts_arg())
         else:
             self._exchange = None
         return plan
+
+    def _counts_arg(self) -> Optional[bool]:
+        return True if self._force_counts else None
 
     # automatic bucket size (bucket_mb=None): 32 MB planes at most (Llama-3-8B:
     # 1 GB of sign bits -> 32 buckets), at least MIN_BUCKETS per step at W > 1
@@ -501,7 +509,11 @@ class Lion(Optimizer):
         if self._plan is not None:
             out["numel"] = sum(s.numel for s in self._plan.segments)
             out["n_buckets"] = len(self._plan.buckets)
-            out["wire_bytes_analytic"] = wire_bytes_per_step(out["numel"], self.last_world, self.exchange_name)
+            out["wire_bytes_analytic"] = wire_bytes_per_step(out["numel"], self.last_world, self.exchange_name,
+                                                             vote=self.vote, counts=self._counts_arg())
+        if self._exchange is not None:
+            out["exchange_impl"] = type(self._exchange).__name__ + (
+                "+counts" if getattr(self._exchange, "use_counts", False) else "")
         if self._elastic is not None:
             out.update(self._elastic.stats())
         if self._agree is not None:

@@ -12,6 +12,14 @@ kernel; they differ in the collective pattern:
     links busy at once instead of one ring neighbour), each rank votes its
     shard (K4 kernel), then ``all_gather_into_tensor`` of the 1-bit result.
     Bytes/rank: 2(W-1)/W·N/8 -- 16x fewer than a bf16 ring all-reduce at W=8.
+    The *average* rule rides the same path for 5 <= W <= 15: the shard vote
+    (K4c) writes each coordinate's live-voter count as P = bit_length(W) bit
+    planes, one ``all_gather_into_tensor`` per bucket collects the ranks'
+    ``[P][shard]`` blocks and the counted apply reads them.  Bytes/rank:
+    (W-1)/W·(1+P)·N/8 (W=8: 4.4 planes against the all-gather's 7), and a
+    P·N/8 receive buffer instead of W·N/8.  At W <= 4 (no fewer bytes) and
+    W > 15 (beyond the bit-sliced counter) average voting keeps the
+    ``allgather`` exchange.
 ``ref_int64``  (reference wire format, A/B only)
     one blocking ``all_gather`` per *parameter tensor* with the packed bytes
     widened to int64, i.e. the reference's 1 byte/param and 148/291 calls per
@@ -123,16 +131,41 @@ class AllGatherExchange(VoteExchange):
         return ApplyArgs(planes=self.recv_view(b), stride=b.nbytes, mode=self.mode)
 
 
+MAX_COUNT_WORLD = 15  # kMaxSliced: the widest world of the bit-sliced vote kernels
+
+
+def counts_supported(world: int) -> bool:
+    return 1 <= world <= MAX_COUNT_WORLD
+
+
+def counts_pay_off(world: int) -> bool:
+    """The count planes move (W-1)/W·(1+P) planes per rank, the all-gather
+    W-1: strictly fewer bytes when 1 + P < W, i.e. from W = 5 on."""
+    return counts_supported(world) and 1 + ref.count_plane_bits(world) < world
+
+
 class AllToAllExchange(VoteExchange):
-    """vote-RS/AG: shard-wise vote after an all-to-all, then 1-bit all-gather."""
+    """vote-RS/AG: shard-wise vote after an all-to-all, then 1-bit all-gather.
+
+    Average voting (W <= 15): the shard vote writes each coordinate's count
+    of live voters as P = bit_length(W) bit planes (K4c) and ONE all-gather per
+    bucket collects every rank's ``[P][shard]`` block into ``[W][P][shard]``,
+    which the counted apply (mode 3) turns into the fractional delta."""
 
     def __init__(self, *a, **k):
         super().__init__(*a, **k)
-        if self.mode == ref.VOTE_AVERAGE:
-            raise ValueError("average voting needs every vote on every rank; use exchange='allgather'")
+        self.use_counts = self.mode == ref.VOTE_AVERAGE
+        if self.use_counts and not counts_supported(self.world):
+            raise ValueError(f"average voting over the all-to-all wire supports at most {MAX_COUNT_WORLD} ranks "
+                             f"(got {self.world}); use exchange='allgather'")
         dev, tb = self.plan.device, self.plan.total_bytes
-        self.need_neg = self.tie == ref.TIE_ZERO
+        self.need_neg = self.tie == ref.TIE_ZERO and not self.use_counts  # the average has no tie rule
         self.recv = torch.zeros(tb, dtype=torch.uint8, device=dev)
+        if self.use_counts:
+            self.n_planes = ref.count_plane_bits(self.world)
+            self.shard_counts = torch.zeros(self.n_planes * tb // self.world, dtype=torch.uint8, device=dev)
+            self.counts = torch.zeros(self.n_planes * tb, dtype=torch.uint8, device=dev)
+            return
         self.voted = torch.zeros(tb, dtype=torch.uint8, device=dev)
         self.shard_pos = torch.zeros(tb // self.world, dtype=torch.uint8, device=dev)
         if self.need_neg:
@@ -142,6 +175,10 @@ class AllToAllExchange(VoteExchange):
     def _v(self, buf, b, scale=1):
         o = b.byte_off // scale
         return buf[o:o + b.nbytes // scale]
+
+    def _counts_v(self, buf, b, scale=1):
+        o = self.n_planes * b.byte_off // scale
+        return buf[o:o + self.n_planes * b.nbytes // scale]
 
     def launch(self, b, alive):
         out = self._v(self.recv, b)
@@ -153,6 +190,13 @@ class AllToAllExchange(VoteExchange):
     def advance(self, b, work, alive):
         work.wait()
         shard = b.nbytes // self.world
+        if self.use_counts:
+            mine = self._counts_v(self.shard_counts, b, self.world)
+            self.executor.vote_count(self._v(self.recv, b), shard, alive, mine, self.ties)
+            work = dist.all_gather_into_tensor(self._counts_v(self.counts, b), mine, group=self.group, async_op=True)
+            moved = (self.world - 1) * self.n_planes * shard
+            self.wire.add(moved, moved)
+            return [work]
         pos = self._v(self.shard_pos, b, self.world)
         neg = self._v(self.shard_neg, b, self.world) if self.need_neg else None
         self.executor.vote_reduce(self._v(self.recv, b), shard, alive, self.tie, pos, neg, self.ties)
@@ -167,6 +211,9 @@ class AllToAllExchange(VoteExchange):
     def finish(self, b, works, alive):
         for w in works:
             w.wait()
+        if self.use_counts:  # [W][P][shard], stride = shard
+            return ApplyArgs(planes=self._counts_v(self.counts, b), stride=b.nbytes // self.world,
+                             mode=ref.VOTE_COUNTED)
         neg = self._v(self.voted_neg, b) if self.need_neg else None
         return ApplyArgs(planes=self._v(self.voted, b), stride=b.nbytes, mode=ref.VOTE_PREVOTED, neg=neg)
 
@@ -192,21 +239,35 @@ class RefInt64Exchange(AllGatherExchange):
         return ApplyArgs(planes=self.recv_view(b), stride=b.nbytes, mode=self.mode)
 
 
+def _average_over_counts(world: int, counts: Optional[bool]) -> bool:
+    """Whether ``a2a`` + average runs over the count planes: by default where
+    its wire is strictly smaller than the all-gather's (W >= 5, W <= 15);
+    ``counts=True`` forces it for any supported world."""
+    return counts_supported(world) if counts else (counts is None and counts_pay_off(world))
+
+
 def make_exchange(strategy: str, plan: FlatPlan, group, rank: int, world: int, executor, tie: int,
-                  mode: int) -> VoteExchange:
+                  mode: int, counts: Optional[bool] = None) -> VoteExchange:
     strategy = canonical_strategy(strategy)
     cls = {"allgather": AllGatherExchange, "a2a": AllToAllExchange, "ref_int64": RefInt64Exchange}[strategy]
-    if strategy == "a2a" and mode == ref.VOTE_AVERAGE:
-        cls = AllGatherExchange
+    if strategy == "a2a" and mode == ref.VOTE_AVERAGE and not _average_over_counts(world, counts):
+        cls = AllGatherExchange  # every rank sees every vote
     return cls(plan, group, rank, world, executor, tie, mode)
 
 
-def wire_bytes_per_step(numel: int, world: int, strategy: str) -> int:
-    """Analytic per-rank receive bytes for reporting."""
+def wire_bytes_per_step(numel: int, world: int, strategy: str, vote: str = "majority",
+                        counts: Optional[bool] = None) -> int:
+    """Analytic per-rank receive bytes of the path that
+    ``make_exchange`` picks for this strategy, vote rule and world."""
     strategy = canonical_strategy(strategy)
     nb = (numel + 7) // 8
     if world <= 1:
         return 0
+    if strategy == "a2a" and ref.VOTE_CODES[vote] == ref.VOTE_AVERAGE:
+        if not _average_over_counts(world, counts):
+            strategy = "allgather"
+        else:  # all-to-all of the sign shards + all-gather of the P count planes
+            return (world - 1) * (1 + ref.count_plane_bits(world)) * nb // world
     if strategy == "allgather":
         return (world - 1) * nb
     if strategy == "a2a":

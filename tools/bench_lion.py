@@ -1,6 +1,7 @@
 """Lion optimizer kernels against the HBM roofline (one MI355X, bf16 params):
 K0 local update, K1 encode (momentum + 1-bit pack), K2 vote+apply over W
-fake voter planes, K4 shard vote (a2a), over the GPT-2 small and the
+fake voter planes, K4 shard vote (a2a), the average vote's byte kernel against
+its a2a path (K4c shard count + counted apply), over the GPT-2 small and the
 Llama-3-8B parameter sets (shapes only, random values).  Bytes per param are
 the kernels' compulsory traffic; prints us, GB/s and % of 6.3 TB/s.
 
@@ -83,6 +84,36 @@ def main():
             hx.vote_reduce(planes[W * b.byte_off: W * b.byte_off + W * sh], sh, alive, ref.TIE_NEGATIVE,
                            voted[b.byte_off // W: b.byte_off // W + sh], None)
 
+    # average vote: the byte kernel over the W gathered planes (all-gather exchange) against the
+    # a2a path's K4c shard count + counted apply from the [W][P][shard] count planes (W <= 15)
+    P = W.bit_length()
+    counted = W <= 15
+    if counted:
+        shard_counts = torch.zeros(P * plan.total_bytes // W, dtype=torch.uint8, device=dev)
+        counts = torch.zeros(P * plan.total_bytes, dtype=torch.uint8, device=dev)
+        for b in plan.buckets:  # true counts of the same planes, shard by shard
+            sh = b.nbytes // W
+            pl = planes[W * b.byte_off: W * (b.byte_off + b.nbytes)].view(W, b.nbytes)
+            for r in range(W):
+                o = P * b.byte_off + r * P * sh
+                hx.vote_count(pl[:, r * sh:(r + 1) * sh].contiguous().view(-1), sh, alive, counts[o:o + P * sh])
+
+    def apply_average():
+        for b in plan.buckets:
+            pl = planes[W * b.byte_off: W * (b.byte_off + b.nbytes)]
+            hx.apply(meta, b, pl, b.nbytes, alive, ref.VOTE_AVERAGE, ref.TIE_NEGATIVE, None, hp)
+
+    def apply_counted():
+        for b in plan.buckets:
+            hx.apply(meta, b, counts[P * b.byte_off: P * (b.byte_off + b.nbytes)], b.nbytes // W, alive,
+                     ref.VOTE_COUNTED, ref.TIE_NEGATIVE, None, hp)
+
+    def vote_count():  # a2a + average: this rank's shard of every bucket, W planes in, P count planes out
+        for b in plan.buckets:
+            sh = b.nbytes // W
+            o = P * b.byte_off // W
+            hx.vote_count(planes[W * b.byte_off: W * b.byte_off + W * sh], sh, alive, shard_counts[o:o + P * sh])
+
     src = torch.empty(n, dtype=torch.bfloat16, device=dev)
     dst = torch.empty_like(src)
 
@@ -94,6 +125,10 @@ def main():
     cases = {"K0 local": (local, 10.0), "K1 encode": (encode, 6.0 + 1 / 8),
              f"K2 vote+apply W={W}": (apply, 4.0 + W / 8), "K2 prevoted apply": (apply_prevoted, 4.0 + 1 / 8), f"K4 shard vote W={W}": (vote_reduce, (W + 1) / 8 / W),
              "bf16 copy (reference)": (copy, 4.0)}
+    cases[f"K2 average (byte kernel) W={W}"] = (apply_average, 4.0 + W / 8)
+    if counted:
+        cases[f"K2 counted apply W={W}"] = (apply_counted, 4.0 + P / 8)
+        cases[f"K4c shard count W={W}"] = (vote_count, (W + P) / 8 / W)
     print(f"{model}: {n / 1e6:.1f}M params, {len(ps)} tensors, {len(plan.buckets)} buckets", flush=True)
     res = {k: [] for k in cases}
     for _ in range(3):
@@ -102,7 +137,7 @@ def main():
     for k, (f, bpp) in cases.items():
         us = statistics.median(res[k])
         gbs = bpp * n / us / 1e3
-        print(f"  {k:22s} {us:9.1f} us  {gbs:7.0f} GB/s  {100 * gbs * 1e9 / HBM:5.1f}% of 6.3 TB/s", flush=True)
+        print(f"  {k:30s} {us:9.1f} us  {gbs:7.0f} GB/s  {100 * gbs * 1e9 / HBM:5.1f}% of 6.3 TB/s", flush=True)
 
 
 if __name__ == "__main__":
