@@ -8,6 +8,10 @@ own scale, with the bound anchored on an fp64 reference and on a rounding
 model -- the fp64 computation with only the bf16 roundings that any bf16-MFMA
 flash algorithm has to perform -- instead of a guessed tolerance.
 docs/TEST_TOLERANCES.md has the measured ratios and the constant ``C_ROWS``.
+
+The second half (``int_operand`` onwards) is the exact-arithmetic GEMM
+conformance: integer operands whose fp32 sums are exact, so the expected
+output is one deterministic rounding and needs no tolerance at all.
 """
 import torch
 
@@ -205,3 +209,236 @@ def check_attention(name, got, q, k, v, dout, p, seed, window=0, cos=None, sin=N
         except AssertionError as e:
             failures.append(str(e))
     assert not failures, "\n".join(failures)
+
+
+# ---------------------------------------------------------------------------
+# Exact-arithmetic GEMM conformance (tests/test_gemm_exact_*.py,
+# docs/TEST_TOLERANCES.md "GEMM").  With small-integer operands (optionally
+# scaled by a power of two) every product and every partial sum of a bf16 GEMM
+# is exact in fp32 whatever the accumulation order, so the expected output is
+# ONE deterministic rounding of an exactly known number and needs no tolerance.
+
+# fp32 holds every integer of magnitude < 2^24
+EXACT_FP32 = 2.0 ** 24
+# eval_floor = EVAL_MARGIN x the error of a plain fp32 evaluation (fixed, see the doc)
+EVAL_MARGIN = 8.0
+# classical bound of a recursive fp32 sum of n terms: n * 2^-24 * sum |x_i|
+SUM_EPS = 2.0 ** -24
+# rows a wave of the NT kernel folds into one bias-gradient partial row
+GEMM_SLAB = 128
+
+
+def int_operand(shape, lo, hi, seed, device, asym="col", scale=1.0):
+    """bf16 [rows, cols] of integers in [lo, hi] times ``scale`` (a power of
+    two: the values, their products and sums stay exact), drawn from a seeded
+    CPU generator so that CPU and GPU tests see the same data.  ``asym`` adds
+    (index % 7) to column 0 ("col") or to row 0 ("row"), so that a transposed
+    or misplaced element cannot cancel; None adds nothing."""
+    g = torch.Generator().manual_seed(seed)
+    t = torch.randint(lo, hi + 1, tuple(shape), generator=g).float()
+    if asym == "col":
+        t[:, 0] += (torch.arange(shape[0]) % 7).float()
+    elif asym == "row":
+        t[0, :] += (torch.arange(shape[1]) % 7).float()
+    else:
+        assert asym is None, asym
+    assert scale > 0 and float(torch.frexp(torch.tensor(float(scale)))[0]) == 0.5, "scale must be a power of two"
+    t = t * scale
+    out = t.to(torch.bfloat16)
+    assert torch.equal(out.float(), t), "operand not exact in bf16"
+    return out.to(device)
+
+
+def _assert_exact(mag64: torch.Tensor, unit: float, what: str):
+    """The exactness condition: sum_k |a_k b_k| (>= |any partial sum, in any
+    order|) stays below 2^24 units, ``unit`` being the power of two the
+    operands' common scale contributes."""
+    worst = float(mag64.max()) / unit if mag64.numel() else 0.0
+    assert worst < EXACT_FP32, f"{what}: max sum |a b| = {worst:.0f} units >= 2^24, fp32 accumulation is not exact"
+
+
+def _unit(*ts) -> float:
+    """Product of the operands' power-of-two scales: the smallest non-zero |value| of each."""
+    u = 1.0
+    for t in ts:
+        nz = t[t != 0]
+        u *= float(nz.abs().min()) if nz.numel() else 1.0
+    return min(u, 1.0)
+
+
+def exact_nt(a, b):
+    """fp64 a [M, K] . b [N, K]^T, asserted exact in fp32 (max |sum| < 2^24)."""
+    a64, b64 = a.detach().double(), b.detach().double()
+    s = a64 @ b64.t()
+    _assert_exact(a64.abs() @ b64.abs().t(), _unit(a64, b64), "exact_nt")
+    return s
+
+
+def exact_tn(P, Q):
+    """fp64 P [k, M]^T . Q [k, N] (tensors or lists of row segments), asserted exact in fp32."""
+    p64 = (torch.cat(list(P)) if isinstance(P, (list, tuple)) else P).detach().double()
+    q64 = (torch.cat(list(Q)) if isinstance(Q, (list, tuple)) else Q).detach().double()
+    s = p64.t() @ q64
+    _assert_exact(p64.abs().t() @ q64.abs(), _unit(p64, q64), "exact_tn")
+    return s
+
+
+def tie_share(sum64: torch.Tensor) -> float:
+    """Fraction of the values that are exact bf16 round-to-nearest ties: 9
+    significant bits with the last one set (odd integers in [256, 512), values
+    = 2 mod 4 in [512, 1024), ...).  Only on those does round-to-nearest-even
+    differ from round-half-up / half-away."""
+    m, _ = torch.frexp(sum64.detach().double().abs())  # |x| = m 2^e, m in [0.5, 1)
+    s = m * 512.0                                       # in [256, 512): 9 bits before the point
+    tie = (s == s.floor()) & (s.floor() % 2 == 1)
+    return float(tie.double().mean()) if tie.numel() else 0.0
+
+
+def bf16_half_ulp(ref64: torch.Tensor) -> torch.Tensor:
+    """Half a bf16 ulp at |ref| (fp64): 2^(floor(log2 |ref|) - 8); 0 at ref = 0.
+    Between 2^-9 |ref| (top of a binade) and 2^-8 |ref| (bottom)."""
+    r = ref64.detach().double().abs()
+    _, e = torch.frexp(r)  # r = m 2^e, m in [0.5, 1): floor(log2 r) = e - 1
+    return torch.where(r > 0, torch.ldexp(torch.ones_like(r), e - 9), torch.zeros_like(r))
+
+
+_K0, _K1 = 0.7978845608028654, 0.044715  # sqrt(2 / pi), the tanh form's kappa
+
+
+def gelu_form(u, exact):
+    """gelu(u) in u's own dtype: the erf form (exact) or the tanh approximation."""
+    if exact:
+        return 0.5 * u * (1.0 + torch.erf(u * 0.7071067811865476))
+    return 0.5 * u * (1.0 + torch.tanh(_K0 * (u + _K1 * u * u * u)))
+
+
+def gelu_grad_form(u, exact):
+    """d gelu(u) / du in u's own dtype, the closed form matching gelu_form."""
+    if exact:
+        return 0.5 * (1.0 + torch.erf(u * 0.7071067811865476)) + u * 0.3989422804014327 * torch.exp(-0.5 * u * u)
+    t = torch.tanh(_K0 * (u + _K1 * u * u * u))
+    return 0.5 * (1.0 + t) + 0.5 * u * (1.0 - t * t) * _K0 * (1.0 + 3.0 * _K1 * u * u)
+
+
+def gelu64(u, exact):
+    return gelu_form(u.detach().double(), exact)
+
+
+def gelu_grad64(u, exact):
+    return gelu_grad_form(u.detach().double(), exact)
+
+
+def eval_floor(fn, u32: torch.Tensor) -> float:
+    """EVAL_MARGIN x max |fn(u32) - fn(fp64(u32))|: the absolute error of a plain
+    fp32 PyTorch evaluation of the closed form ``fn`` on the test's own u.  The
+    allowance for evaluating the form in fp32 is anchored on the reference's
+    arithmetic, never on the kernel's result."""
+    u32 = u32.detach().float()
+    if u32.numel() == 0:
+        return 0.0
+    return EVAL_MARGIN * float((fn(u32).double() - fn(u32.double())).abs().max())
+
+
+def assert_rounded(got, ref64, floor, name=""):
+    """Elementwise |got - ref| <= half a bf16 ulp of ref + floor (a float or a
+    tensor): ``got`` is the round-to-nearest bf16 of a value within ``floor`` of
+    ref.  The half ulp is taken exactly, 2^(floor(log2 |ref|) - 8): the flat
+    2^-9 |ref| is half an ulp only at the top of a binade and rejects bf16(ref)
+    itself at the bottom (by up to 2x; test_gemm_exact_cpu shows it), so the
+    ratio against 2^-9 |ref| + floor is printed next to the asserted one.
+    Prints and returns the largest err / bound."""
+    g, r = got.detach().double(), ref64.detach().double()
+    assert g.shape == r.shape, f"{name}: shape {tuple(g.shape)} vs {tuple(r.shape)}"
+    assert torch.isfinite(g).all(), f"{name}: non-finite values"
+    err = (g - r).abs()
+    fl = floor.detach().double() if torch.is_tensor(floor) else float(floor)
+    bound = bf16_half_ulp(r) + fl
+    ratio = torch.where(err == 0, torch.zeros_like(err), err / bound)
+    flat = torch.where(err == 0, torch.zeros_like(err), err / (HALF_ULP_BF16 * r.abs() + fl))
+    worst = float(ratio.max()) if ratio.numel() else 0.0
+    worst_flat = float(flat.max()) if flat.numel() else 0.0
+    # the share of the floor that the error left over after half an ulp takes up (0: rounding alone explains got)
+    over = (err - bf16_half_ulp(r)).clamp_min(0.0)
+    used = torch.where(over == 0, torch.zeros_like(over), over / (fl if torch.is_tensor(fl) else torch.full_like(over, fl)))
+    used = float(used.max()) if used.numel() else 0.0
+    print(f"[rounded] {name}: max err / bound {worst:.3f}, floor used {used:.3f} "
+          f"(against the flat 2^-9 |ref| + floor: {worst_flat:.3f})")
+    if not worst <= 1.0:
+        gf, rf, rr = g.reshape(-1), r.reshape(-1), ratio.reshape(-1)
+        nbad = int((~(ratio <= 1)).sum())
+        rows = _worst(ratio, lambda i, pos: f"  elem {pos}: got {float(gf[i]):.6e}  ref {float(rf[i]):.6e}  "
+                      f"err / bound {float(rr[i]):.2f}")
+        raise AssertionError(f"{name}: {nbad} of {ratio.numel()} elements over half a bf16 ulp + floor; worst:\n{rows}")
+    return worst
+
+
+def expect_nt(sum64, bias=None):
+    """bf16(fp32(sum) + fp32(bias)): the one rounding of the NT GEMM's plain / bias epilogue."""
+    s = sum64.float()
+    assert torch.equal(s.double(), sum64), "sum not exact in fp32"
+    return (s if bias is None else s + bias.float()).to(torch.bfloat16)
+
+
+def gemm_slabs(M):
+    """Row ranges of the NT kernel's bias-gradient partial rows: slab s = part[2 tm + wr]
+    covers rows [128 s, 128 s + 128) of [0, M); 2 * ceil(M / 256) slabs, the trailing ones may be empty."""
+    return [slice(min(GEMM_SLAB * s, M), min(GEMM_SLAB * (s + 1), M)) for s in range(2 * ((M + 255) // 256))]
+
+
+def strided_rows(rows, parts):
+    """Row sets of bias_gelu_bwd's partial rows: block p walks rows p, p + parts, ..."""
+    return [torch.arange(p, max(rows, p), parts) for p in range(parts)]
+
+
+def assert_col_partials(part, dz, row_sets, nterms=None, exact=False, name=""):
+    """part [len(row_sets), N] fp32 against the fp64 column sums of the kernel's
+    own bf16 ``dz`` over each row set (slices or index tensors).  ``exact``:
+    bit-equal (integer-valued dz, sums below 2^24).  Otherwise per column
+    |part[s] - sum dz| <= n * 2^-24 * sum |dz| with n = ``nterms`` (or the row
+    set's size): the classical bound of an fp32 sum of n terms in any order.
+    A set with no rows has bound 0: its partial row must be exactly zero.
+    Prints and returns the largest err / bound."""
+    assert part.dtype == torch.float32, part.dtype
+    assert tuple(part.shape) == (len(row_sets), dz.shape[1]), \
+        f"{name}: part shape {tuple(part.shape)}, expected {(len(row_sets), dz.shape[1])}"
+    assert torch.isfinite(part).all(), f"{name}: non-finite partials"
+    p64, d64 = part.detach().double(), dz.detach().double()
+    worst, bad = 0.0, []
+    for s, rows in enumerate(row_sets):
+        blk = d64[rows] if isinstance(rows, slice) else d64[rows.to(d64.device)]
+        n = blk.shape[0] if nterms is None else nterms
+        col, mag = blk.sum(0), blk.abs().sum(0)
+        err = (p64[s] - col).abs()
+        if blk.shape[0] == 0:
+            assert bool((part[s] == 0).all()), f"{name}: partial row {s} has no valid rows but is not zero"
+            continue
+        if exact:
+            assert float(mag.max()) < EXACT_FP32, f"{name}: slab {s} column sums are not exact in fp32"
+            bound = torch.zeros_like(col)
+        else:
+            bound = n * SUM_EPS * mag
+        ok = err <= bound
+        # exact: the figure is the largest |error| itself
+        ratio = err if exact else torch.where(err == 0, torch.zeros_like(err), err / bound.clamp_min(1e-300))
+        worst = max(worst, float(ratio.max()))
+        if not bool(ok.all()):
+            j = int(torch.argmax(ratio))
+            bad.append(f"  partial row {s}: {int((~ok).sum())} columns off; column {j}: got {float(p64[s, j]):.9e}  "
+                       f"sum of dz {float(col[j]):.9e}  bound {float(bound[j]):.3e}")
+    print(f"[partials] {name}: " + (f"max |err| {worst:g} (bit-exact sums)" if exact else f"max err / bound {worst:.3f}"))
+    assert not bad, f"{name}: bias-gradient partials do not match the column sums of dz:\n" + "\n".join(bad[:5])
+    return worst
+
+
+def assert_bits(got, exp, name=""):
+    """Bit-equal tensors of one dtype (NaN, the sign of zero and every rounding included)."""
+    assert got.shape == exp.shape and got.dtype == exp.dtype, \
+        f"{name}: {tuple(got.shape)} {got.dtype} vs {tuple(exp.shape)} {exp.dtype}"
+    view = {2: torch.int16, 4: torch.int32, 8: torch.int64}[got.element_size()]
+    same = got.contiguous().view(view) == exp.contiguous().view(view)
+    if not bool(same.all()):
+        bad = ~same
+        diff = (got.double() - exp.double()).abs()[bad]
+        i = tuple(int(j) for j in bad.nonzero()[0])
+        raise AssertionError(f"{name}: {int(bad.sum())} of {bad.numel()} elements differ, max |diff| "
+                             f"{float(diff.max()):.6g}; first at {i}: got {float(got[i])!r} expected {float(exp[i])!r}")

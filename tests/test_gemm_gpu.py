@@ -29,7 +29,7 @@ def _check(got, ref, K):
 
 @pytest.mark.parametrize("M,N,K", [(256, 256, 128), (512, 768, 768), (20480 // 8, 2304, 768), (300, 136, 256),
                                    (1000, 50304 // 4, 768), (2048, 768, 3072),
-                                   # > 256 tiles: persistent blocks walk several tiles (edge tiles too)
+                                   # > 256 tiles, one block per tile: more blocks than CUs (edge tiles too)
                                    (4160, 4352, 256), (8448, 2048, 128), (5000, 3000, 384)])
 def test_gemm_nt_plain_and_bias(M, N, K):
     ops = _ops()
