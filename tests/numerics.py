@@ -434,7 +434,7 @@ def assert_bits(got, exp, name=""):
     """Bit-equal tensors of one dtype (NaN, the sign of zero and every rounding included)."""
     assert got.shape == exp.shape and got.dtype == exp.dtype, \
         f"{name}: {tuple(got.shape)} {got.dtype} vs {tuple(exp.shape)} {exp.dtype}"
-    view = {2: torch.int16, 4: torch.int32, 8: torch.int64}[got.element_size()]
+    view = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[got.element_size()]
     same = got.contiguous().view(view) == exp.contiguous().view(view)
     if not bool(same.all()):
         bad = ~same
@@ -442,3 +442,97 @@ def assert_bits(got, exp, name=""):
         i = tuple(int(j) for j in bad.nonzero()[0])
         raise AssertionError(f"{name}: {int(bad.sum())} of {bad.numel()} elements differ, max |diff| "
                              f"{float(diff.max()):.6g}; first at {i}: got {float(got[i])!r} expected {float(exp[i])!r}")
+
+
+# ---------------------------------------------------------------------------
+# LoRA adapter kernels (tests/test_lora_exact_*.py, docs/TEST_TOLERANCES.md
+# "LoRA and 4-bit").  The dropout constants, the row ranges of the fp32
+# partials and the checks of the two-operand partial sums.
+
+def drop_consts(p: float):
+    """(thresh16, inv_keep) as the bindings derive them from p: an element is
+    kept when its 16-bit draw >= thresh16, inv_keep = fp32(65536 / (65536 - thresh16))
+    (exactly 2 at p = 0.5 and 4 at p = 0.75)."""
+    th = min(65535, int(p * 65536.0 + 0.5))
+    return th, float(torch.tensor(65536.0 / (65536.0 - th), dtype=torch.float32))
+
+
+def lora_parts(rows: int, N: int):
+    """(P, rpp, ranges) of lora_cols' partials by the documented rule: P =
+    min(512 // cblocks, ceil(rows / 16)) but at least 1 with cblocks = ceil(N /
+    512), rpp = ceil(rows / P), part p sums the rows [p rpp, min((p + 1) rpp,
+    rows)) -- an empty range where p rpp >= rows."""
+    cblocks = (N + 511) // 512
+    P = max(1, min(512 // cblocks, (rows + 15) // 16))
+    rpp = (rows + P - 1) // P
+    return P, rpp, [(min(p * rpp, rows), min((p + 1) * rpp, rows)) for p in range(P)]
+
+
+def part_sums64(g, y, ranges, layout):
+    """fp64 sums over each contiguous row range of g[t, n] * y[t, j] and of
+    their magnitudes: [P, N, R] (layout "nr", the layout of B) or [P, R, N]
+    ("rn", the layout of A)."""
+    assert layout in ("nr", "rn"), layout
+    g64, y64 = g.detach().cpu().double(), y.detach().cpu().double()
+    rows, P = g64.shape[0], len(ranges)
+    rpp = max(max(r1 - r0 for r0, r1 in ranges), 1)
+    assert all(r0 == min(p * rpp, rows) and r1 == min((p + 1) * rpp, rows) for p, (r0, r1) in enumerate(ranges))
+    pad = max(P * rpp - rows, 0)
+    gp = torch.nn.functional.pad(g64, (0, 0, 0, pad))[:P * rpp].view(P, rpp, -1)
+    yp = torch.nn.functional.pad(y64, (0, 0, 0, pad))[:P * rpp].view(P, rpp, -1)
+    eq = "ptn,ptj->pnj" if layout == "nr" else "ptn,ptj->pjn"
+    return torch.einsum(eq, gp, yp), torch.einsum(eq, gp.abs(), yp.abs())
+
+
+def assert_part_sums(part, g, y, ranges, layout, yscale=1.0, exact=False, name=""):
+    """part (fp32, [P, N, R] or [P, R, N]) against yscale * the fp64 sums of
+    g[t, n] * y[t, j] over each part's own row range.  ``exact``: bit-equal
+    (operands whose sums stay below 2^24 units, yscale a power of two).
+    Otherwise |part - ref| <= n * 2^-24 * yscale * sum |g y| with n the rows of
+    the range: n - 1 additions in any order and one rounding for the scaling
+    (the product of two bf16 is exact in fp32).  A part without rows has bound
+    0 either way and must be +0 throughout.  Prints and returns the worst err / bound."""
+    assert part.dtype == torch.float32, part.dtype
+    s, mag = part_sums64(g, y, ranges, layout)
+    assert tuple(part.shape) == tuple(s.shape), f"{name}: part shape {tuple(part.shape)}, expected {tuple(s.shape)}"
+    assert torch.isfinite(part).all(), f"{name}: non-finite partials"
+    p_cpu = part.detach().cpu()
+    empty = torch.tensor([r1 <= r0 for r0, r1 in ranges])
+    if bool(empty.any()):
+        z = p_cpu[empty]
+        assert_bits(z, torch.zeros_like(z), f"{name}: parts without rows")
+    if exact:
+        _assert_exact(mag, _unit(g.detach().cpu().double(), y.detach().cpu().double()), f"{name}: part sums")
+        exp = (s * yscale).float() + 0.0  # a zero sum is +0 in the kernel (the accumulators start at +0)
+        assert torch.equal(exp.double(), s * yscale), f"{name}: scaled sums not exact in fp32"
+        assert_bits(p_cpu, exp.cpu(), name)
+        print(f"[parts] {name}: {len(ranges)} parts ({int(empty.sum())} empty) bit-exact")
+        return 0.0
+    n = torch.tensor([max(r1 - r0, 0) for r0, r1 in ranges], dtype=torch.float64).view(-1, 1, 1)
+    bound = n * SUM_EPS * abs(yscale) * mag.cpu()
+    err = (p_cpu.double() - (s * yscale).cpu()).abs()
+    ratio = torch.where(err == 0, torch.zeros_like(err), err / bound.clamp_min(1e-300))
+    worst = float(ratio.max()) if ratio.numel() else 0.0
+    print(f"[parts] {name}: max err / bound {worst:.3f} ({len(ranges)} parts, {int(empty.sum())} empty)")
+    if not worst <= 1.0:
+        i = tuple(int(j) for j in (ratio > 1).nonzero()[0])
+        raise AssertionError(f"{name}: {int((ratio > 1).sum())} of {ratio.numel()} partial sums over n * 2^-24 * sum |terms|; "
+                             f"first at {i}: got {float(p_cpu[i]):.9e}  ref {float((s * yscale)[i]):.9e}  "
+                             f"bound {float(bound[i]):.3e}")
+    return worst
+
+
+def assert_within(got, ref64, bound, name=""):
+    """Elementwise |got - ref| <= bound (an fp64 tensor); prints and returns the worst err / bound."""
+    g, r, b = got.detach().double().cpu(), ref64.detach().double().cpu(), bound.detach().double().cpu()
+    assert g.shape == r.shape, f"{name}: shape {tuple(g.shape)} vs {tuple(r.shape)}"
+    assert torch.isfinite(g).all(), f"{name}: non-finite values"
+    err = (g - r).abs()
+    ratio = torch.where(err == 0, torch.zeros_like(err), err / b.clamp_min(1e-300))
+    worst = float(ratio.max()) if ratio.numel() else 0.0
+    print(f"[within] {name}: max err / bound {worst:.3f}")
+    if not worst <= 1.0:
+        i = tuple(int(j) for j in (ratio > 1).nonzero()[0])
+        raise AssertionError(f"{name}: {int((ratio > 1).sum())} of {ratio.numel()} elements over the bound; first at {i}: "
+                             f"got {float(g[i]):.6e}  ref {float(r[i]):.6e}  bound {float(b[i]):.3e}")
+    return worst

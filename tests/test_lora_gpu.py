@@ -7,6 +7,8 @@ import torch
 from distributed_lion_pytorch_amd.models.lora import LoraConfig, inject_lora
 from distributed_lion_pytorch_amd.ops import fused, hip
 from distributed_lion_pytorch_amd.ops import linear as L
+from lora_exact_cases import chain_bounds
+from numerics import assert_bits, assert_rounded
 
 pytestmark = pytest.mark.gpu
 
@@ -41,6 +43,12 @@ def test_lora_add_matches_fp32(cuda, r, p):
     assert _rel(a.grad, ar.grad) < 2e-2
     assert _rel(b.grad, br.grad) < 2e-2
     assert torch.equal(o.grad, dout)
+    # every element on its own scale: fp64 references with the two bf16 intermediates' errors propagated
+    # (lora_exact_cases.chain_bounds), instead of the tensor's maximum
+    cb = chain_bounds(x, o, a, b, dout, s, p, seed)
+    for name, got in (("out", out), ("dx", x.grad), ("dA", a.grad), ("dB", b.grad)):
+        assert_rounded(got.detach().cpu(), cb[name][0], cb[name][1], f"lora_add {name} r={r} p={p}")
+    assert_bits(o.grad, dout, "lora_add do")
 
 
 def test_lora_dropout_mask_is_fresh_per_call(cuda):

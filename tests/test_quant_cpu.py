@@ -19,6 +19,9 @@ from distributed_lion_pytorch_amd.models.quant import (Linear4bit, QuantConfig, 
                                                        quantized_bytes)
 from distributed_lion_pytorch_amd.ops.quant import (NF4_CODE, code_tensor, dequantize_4bit, dequantize_4bit_ref,
                                                     quantize_4bit, quantize_4bit_ref)
+from numerics import assert_bits
+from quant_edge_cases import (DEQUANT_WORDS, DTYPES, EDGE_ABSMAX, crafted_blocks, edge_packed, random_packed,
+                              tie_points)
 
 
 @pytest.mark.parametrize("qt", ["nf4", "fp4"])
@@ -176,3 +179,128 @@ def test_quantize_after_lora_keeps_adapters_trainable():
     ids = torch.randint(0, 512, (1, 64))
     m(input_ids=ids, labels=ids).loss.backward()
     assert q.lora_B.weight.grad is not None
+
+
+# ---------------------------------------------------------------------------
+# The hand-built inputs of test_quant_gpu.py's edge cases (quant_edge_cases.py):
+# they contain the ties and the fp16 range ends they claim, and the bit
+# comparison against the oracle rejects the two planted defects.
+
+
+def _quantize_last_minimum(w, code):
+    """quantize_4bit_ref with the tie rule ``<=``: the LAST minimum wins."""
+    blocks = w.detach().reshape(-1, 64).float()
+    absmax = blocks.abs().amax(dim=1)
+    safe = torch.where(absmax > 0, absmax, torch.ones_like(absmax))
+    x = torch.where(absmax[:, None] > 0, blocks / safe[:, None], torch.zeros_like(blocks))
+    idx = (15 - (x.unsqueeze(-1) - code).abs().flip(-1).argmin(dim=-1)).to(torch.uint8).reshape(-1, 2)
+    return ((idx[:, 0] << 4) | idx[:, 1]).contiguous(), absmax
+
+
+def test_tie_points_are_true_ties():
+    fp4, nf4 = tie_points("fp4"), tie_points("nf4")
+    h = float(code_tensor("fp4")[1]) / 2
+    assert fp4 == [-h, h] and len(nf4) == 6
+    for qt, pts in (("fp4", fp4), ("nf4", nf4)):
+        code = code_tensor(qt)
+        for t in pts:
+            d = (torch.tensor(t) - code).abs()
+            assert int((d == d.min()).sum()) >= 2, (qt, t)
+    # 0.375 is midway between FP4's 0.25 and 0.5 in exact arithmetic, but 0.3333 (index 4) is nearer: no tie
+    code = code_tensor("fp4")
+    d = (torch.tensor(0.375) - code).abs()
+    assert d[7] == d[5] == 0.125 and int(d.argmin()) == 4 and d[4] < 0.05
+    # x = 0 under FP4: +0 (index 0) and -0 (index 8) are both at distance 0
+    d0 = (torch.tensor(0.0) - code).abs()
+    assert d0[0] == 0 and d0[8] == 0 and int(d0.argmin()) == 0
+    # the negative half-step is a three-way tie
+    dn = (torch.tensor(-h) - code).abs()
+    assert dn[0] == dn[8] == dn[9] == dn.min()
+
+
+@pytest.mark.parametrize("qt", ["nf4", "fp4"])
+@pytest.mark.parametrize("dt", DTYPES)
+def test_crafted_blocks_hold_what_they_claim(dt, qt):
+    w = crafted_blocks(qt, dt)
+    f = w.float()
+    assert w.shape == (9, 64) and f[0].abs().max() == 1 and f[2].abs().max() == 3 and f[2].min() == -3
+    assert bool((f[1] == 0).sum() == 63) and bool(torch.signbit(f[1]).any()) and bool((~torch.signbit(f[1])).any())
+    assert f[3].unique().numel() == 1 and f[4].unique().numel() == 1 and bool((f[5] == 0).all())
+    tiny = torch.finfo(dt).tiny
+    if dt != torch.float32:
+        assert bool(((f[7] != 0) & (f[7].abs() < tiny)).sum() == 63)  # subnormals of dt
+    assert float(f[6].abs().max()) >= (65504.0 if dt == torch.float16 else 3.0e38)
+    # defect: tie rule <= instead of <.  Differs from the oracle in the crafted tie blocks and nowhere else
+    code = code_tensor(qt)
+    q, a = quantize_4bit_ref(w, code)
+    ql, al = _quantize_last_minimum(w, code)
+    assert torch.equal(a, al)
+    differ = (q != ql).view(-1, 32).any(1)
+    expect = torch.zeros(9, dtype=torch.bool)
+    if qt == "fp4":
+        expect[[0, 1, 5, 8]] = True  # every block with an exact zero (0 ties with -0), and block 0's half steps
+        expect[2] = bool((f[2] == 0).any())
+        expect[7] = bool((f[7] == 0).any())
+        expect[6] = bool((f[6] == 0).any())
+    elif dt == torch.float32:
+        expect[0] = True  # NF4's fp32-exact midpoints
+    assert torch.equal(differ, expect), differ
+    if bool(expect.any()):
+        with pytest.raises(AssertionError, match="elements differ"):
+            assert_bits(ql, q, "last minimum")
+    # ... on random weights the two rules agree under NF4 (the old tests could not tell them apart); under FP4
+    # they differ almost only in which zero is taken (index 0 or 8: every x nearest to 0 is a tie of +0 and -0)
+    torch.manual_seed(0)
+    wr = (torch.randn(384, 1024) * 0.02).to(dt)
+    qa, qb = _quantize_last_minimum(wr, code)[0], quantize_4bit_ref(wr, code)[0]
+    if qt == "nf4":
+        assert torch.equal(qa, qb)
+    else:
+        ia, ib = torch.stack([qa >> 4, qa & 15], 1), torch.stack([qb >> 4, qb & 15], 1)
+        diff = ia != ib
+        assert bool(diff.any()) and float(((ia == 8) & (ib == 0))[diff].double().mean()) > 0.99
+
+
+def _to_f16_flushing(v32):
+    h = v32.to(torch.float16)
+    return torch.where(h.abs() < 2.0 ** -14, torch.copysign(torch.zeros_like(h), h), h)
+
+
+@pytest.mark.parametrize("qt", ["nf4", "fp4"])
+def test_edge_packed_reaches_the_fp16_range_ends(qt):
+    q, absmax = edge_packed()
+    assert torch.equal(torch.unique(q), torch.arange(256, dtype=torch.uint8)) and absmax.unique().numel() == len(EDGE_ABSMAX)
+    code = code_tensor(qt)
+    v32 = dequantize_4bit_ref(q, absmax, code, torch.float32)
+    h = dequantize_4bit_ref(q, absmax, code, torch.float16)
+    assert torch.isfinite(v32).all() and torch.isfinite(dequantize_4bit_ref(q, absmax, code, torch.bfloat16).float()).all()
+    sub = (h != 0) & (h.abs() < 2.0 ** -14)
+    under = (h == 0) & (v32 != 0)
+    assert bool(sub.any()) and bool((under & torch.signbit(h)).any()) and bool((under & ~torch.signbit(h)).any())
+    assert bool((h == float("inf")).any()) and bool((h == float("-inf")).any())
+    assert bool((h.float() != v32)[torch.isfinite(h) & ~sub & ~under].any())  # normal results that had to round
+    one = code == 1.0
+    for am, want in ((65504.0, 65504.0), (65519.0, 65504.0), (65520.0, float("inf")), (3.0e38, float("inf"))):
+        got = (code[one] * torch.tensor(am)).to(torch.float16)
+        assert float(got) == want, (am, float(got))
+        assert bool(((absmax.repeat_interleave(64) == am) & (h == want)).any())
+    # 0.0052 * 0.005 is already an fp16 subnormal
+    if qt == "fp4":
+        v = (code[1] * torch.tensor(0.005)).to(torch.float16)
+        assert 0 < float(v) < 2.0 ** -14
+    # defect: fp16 subnormals flushed to zero -- rejected by the bit comparison; equal on ordinary weights
+    with pytest.raises(AssertionError, match="elements differ"):
+        assert_bits(_to_f16_flushing(v32), h, "flushed")
+    torch.manual_seed(0)
+    qr, ar = quantize_4bit_ref(torch.randn(64, 1024) * 0.02, code_tensor("nf4"))
+    vr = dequantize_4bit_ref(qr, ar, code_tensor("nf4"), torch.float32)
+    nz = vr != 0
+    assert torch.equal(_to_f16_flushing(vr)[nz], vr.to(torch.float16)[nz])
+
+
+def test_dequant_sizes_leave_one_two_and_three_live_steps():
+    live = [((w % 1024) + 255) // 256 for w in DEQUANT_WORDS]
+    assert DEQUANT_WORDS[:3] == [64 // 8, 64 * 129 // 8, (8 * (1024 * 3 + 5) + 63) // 64 * 64 // 8]
+    assert sorted(set(live)) == [1, 2, 3] and all(w % 1024 % 256 != 0 for w in DEQUANT_WORDS)
+    q, a = random_packed(5, 0)
+    assert q.numel() == 160 and a.numel() == 5 and bool((a > 0).all())

@@ -11,6 +11,9 @@ from distributed_lion_pytorch_amd.models.quant import Linear4bit, QuantConfig, d
 from distributed_lion_pytorch_amd.ops import hip
 from distributed_lion_pytorch_amd.ops.quant import (code_tensor, dequantize_4bit, dequantize_4bit_ref, quantize_4bit,
                                                     quantize_4bit_ref)
+from numerics import assert_bits
+from quant_edge_cases import (DEQUANT_T_SHAPES, DEQUANT_WORDS, DTYPES, EDGE_ABSMAX, QUANT_BLOCKS, crafted_blocks,
+                              edge_packed, random_packed, tie_points)
 
 pytestmark = pytest.mark.gpu
 
@@ -114,3 +117,130 @@ def test_dequant4_transposed_into_column_blocks(cuda):
     hip.ops().dequant4_t_(q, a, code, big[:, 1024:2048])
     assert torch.equal(big[:, 1024:2048], full.t())
     assert (big[:, :1024] == 5).all() and (big[:, 2048:] == 5).all()
+
+
+# ---------------------------------------------------------------------------
+# Edges of csrc/quant.hip (docs/TEST_TOLERANCES.md "LoRA and 4-bit"): sizes
+# that make the tail guards fire, crafted blocks for the tie rule and the sign
+# of zero, and hand-built packed inputs that drive the fp16 expansion to
+# subnormals, underflow and overflow.  Everything is bit-exact against the
+# PyTorch oracle, evaluated on the GPU and on a CPU copy of the inputs, so the
+# expectation does not depend on the GPU's PyTorch.
+
+
+def _check_quant4(w, qt, name):
+    """quant4 on the GPU copy of ``w`` (CPU) == the oracle on the GPU == the oracle on the CPU."""
+    hip.require()
+    dev = torch.device("cuda", 0)
+    wg = w.to(dev)
+    q, a = hip.ops().quant4(wg, code_tensor(qt, dev))
+    assert q.dtype == torch.uint8 and q.shape == (w.numel() // 2,) and a.shape == (w.numel() // 64,)
+    for where, (qr, ar) in (("gpu oracle", quantize_4bit_ref(wg, code_tensor(qt, dev))),
+                            ("cpu oracle", quantize_4bit_ref(w, code_tensor(qt)))):
+        assert_bits(a.cpu(), ar.cpu(), f"{name} absmax vs {where}")
+        bad = (q.cpu() != qr.cpu()).nonzero().flatten().tolist()
+        assert not bad, (f"{name}: {len(bad)} bytes differ from the {where}; first: byte {bad[0]} (block {bad[0] // 32}) "
+                         f"got {int(q[bad[0]]):#04x} expected {int(qr[bad[0]]):#04x}")
+    return q, a
+
+
+@pytest.mark.parametrize("qt", ["nf4", "fp4"])
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("nblocks", QUANT_BLOCKS)
+def test_quant4_block_counts(cuda, nblocks, dt, qt):
+    """1, 255, 256, 257 blocks: the b >= nblocks guard with 255, 1, 0 and 255 idle threads."""
+    g = torch.Generator().manual_seed(nblocks)
+    w = (torch.randn(nblocks, 64, generator=g) * 0.02).to(dt)
+    _check_quant4(w, qt, f"quant4 {nblocks} blocks {dt} {qt}")
+
+
+@pytest.mark.parametrize("qt", ["nf4", "fp4"])
+@pytest.mark.parametrize("dt", DTYPES)
+def test_quant4_crafted_blocks(cuda, dt, qt):
+    """Blocks of absmax 1 holding the exact midpoints between two nearest codes (first minimum wins; six of NF4's
+    adjacent pairs have an fp32-exact midpoint, FP4 has +-code[1] / 2 -- the negative one a three-way tie with +0
+    and -0 -- and x = 0 itself, equidistant from index 0 and index 8), +-0.0 inputs, a negative maximum, a repeated
+    value, an all-zero block next to the largest finite values, subnormal inputs.  0.375 is midway between FP4's
+    0.25 and 0.5 but nearest to 0.3333 (index 4): no tie, it is in the block all the same.  NaN and inf inputs are
+    out of scope: the oracle's argmin over NaN distances is not a contract the kernel follows."""
+    w = crafted_blocks(qt, dt)
+    q, a = _check_quant4(w, qt, f"quant4 crafted {dt} {qt}")
+    idx = torch.stack([q.cpu() >> 4, q.cpu() & 15], 1).reshape(-1, 64)
+    if qt == "fp4":
+        zero = (w[1].float() == 0).nonzero().flatten()
+        assert zero.numel() == 63 and bool((idx[1][zero] == 0).all())  # +0 and -0 both go to index 0, never to 8
+        assert bool((idx[0][w[0].float() == 0.375] == 4).all())
+        if dt == torch.float32:
+            half = w[0].abs() == tie_points("fp4")[1]
+            assert int(half.sum()) >= 2 and bool((idx[0][half] == 0).all())  # not 1, 8 or 9
+    elif dt == torch.float32:
+        code = code_tensor("nf4")
+        for t in tie_points("nf4"):
+            lo = int((code < t).sum()) - 1  # the lower neighbour has the smaller index in NF4's ascending table
+            hit = w[0] == t
+            assert int(hit.sum()) >= 1 and bool((idx[0][hit] == lo).all()), t
+    assert a[5] == 0 and bool((q.cpu().view(-1, 32)[5] == (0x77 if qt == "nf4" else 0x00)).all())
+
+
+def _check_dequant4(q, absmax, qt, dt, name):
+    hip.require()
+    dev = torch.device("cuda", 0)
+    out = torch.empty(2 * q.numel(), dtype=dt, device=dev)
+    hip.ops().dequant4_(q.to(dev), absmax.to(dev), code_tensor(qt, dev), out)
+    assert_bits(out.cpu(), dequantize_4bit_ref(q.to(dev), absmax.to(dev), code_tensor(qt, dev), dt).cpu(), f"{name} vs gpu oracle")
+    exp = dequantize_4bit_ref(q, absmax, code_tensor(qt), dt)
+    assert_bits(out.cpu(), exp, f"{name} vs cpu oracle")
+    return exp
+
+
+@pytest.mark.parametrize("qt", ["nf4", "fp4"])
+@pytest.mark.parametrize("dt", DTYPES)
+def test_dequant4_every_byte_every_scale(cuda, dt, qt):
+    """Every byte value under absmax = 2^-30 .. 2^17, 0.005, 65504, 65519, 65520, 3e38: in fp16 the products round,
+    fall into the subnormals, underflow to +-0 (sign kept) and overflow to +-inf exactly as PyTorch's conversion."""
+    q, absmax = edge_packed()
+    exp = _check_dequant4(q, absmax, qt, dt, f"dequant4 edges {dt} {qt}")
+    if dt == torch.float16:
+        assert bool(torch.isinf(exp).any()) and bool(((exp != 0) & (exp.abs() < 2.0 ** -14)).any())
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("words", DEQUANT_WORDS)
+def test_dequant4_tail_sizes(cuda, words, dt):
+    """Word counts that are no multiple of 1024: the i < words guards fire with 1, 2 and 3 live steps."""
+    assert words % 8 == 0 and words % 1024 != 0
+    q, absmax = random_packed(words // 8, words)
+    _check_dequant4(q, absmax, "nf4", dt, f"dequant4 {words} words {dt}")
+
+
+@pytest.mark.parametrize("qt", ["nf4", "fp4"])
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("N,K", DEQUANT_T_SHAPES)
+def test_dequant4_transposed_edges(cuda, N, K, dt, qt):
+    """The transposed expansion into a column block between sentinel columns == the oracle's [N, K] transposed,
+    on hand-built bytes and absmax values (every byte value, the fp16 range ends)."""
+    hip.require()
+    nb = N * K // 64
+    i = torch.arange(nb * 32)
+    q = ((i * 37 + i // 256) % 256).to(torch.uint8)  # every byte value, shifting against the blocks
+    absmax = torch.tensor(EDGE_ABSMAX, dtype=torch.float32)[torch.arange(nb) % len(EDGE_ABSMAX)]
+    assert nb >= len(EDGE_ABSMAX) and torch.unique(q).numel() == 256
+    exp = dequantize_4bit_ref(q, absmax, code_tensor(qt), dt).view(N, K).t()
+    big = torch.full((K, N + 24), 5.0, device=cuda, dtype=dt)
+    hip.ops().dequant4_t_(q.to(cuda), absmax.to(cuda), code_tensor(qt, cuda), big[:, 8:8 + N])
+    assert_bits(big[:, 8:8 + N].cpu().contiguous(), exp.contiguous(), f"dequant4_t {N}x{K} {dt} {qt}")
+    assert bool((big[:, :8] == 5).all()) and bool((big[:, 8 + N:] == 5).all())
+
+
+def test_dequant4_transposed_refuses_bad_shapes(cuda):
+    """N % 64 != 0, K % 128 != 0 and an fp32 out raise before anything is launched."""
+    hip.require()
+    code = code_tensor("nf4", cuda)
+    for N, K, dt in [(32, 128, torch.bfloat16), (64, 64, torch.bfloat16), (96, 256, torch.float16),
+                     (64, 128, torch.float32)]:
+        q = torch.zeros(N * K // 2, dtype=torch.uint8, device=cuda)
+        absmax = torch.ones(N * K // 64, device=cuda)
+        out = torch.full((K, N), 3.0, device=cuda, dtype=dt)
+        with pytest.raises(RuntimeError, match="dlion|dequant4_t"):
+            hip.ops().dequant4_t_(q, absmax, code, out)
+        assert bool((out == 3).all())
