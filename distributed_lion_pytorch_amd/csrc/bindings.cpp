@@ -44,17 +44,26 @@ const float* gscale_ptr(const std::optional<Tensor>& gscale) {
   return gscale->data_ptr<float>();
 }
 
+// parameter store rounding: 0 nearest, 1 stochastic (bf16; a no-op for fp32, refused for fp16: dtype code 2)
+void check_rounding(int64_t rounding, int64_t dtype, int64_t coord_base) {
+  TORCH_CHECK(rounding == 0 || rounding == 1, "dlion: bad parameter rounding mode ", rounding);
+  TORCH_CHECK(rounding == 0 || dtype != 2, "dlion: stochastic parameter rounding does not support fp16");
+  TORCH_CHECK(coord_base >= 0 && coord_base % 8 == 0, "dlion: the coordinate base must be a multiple of 8");
+}
+
 void lion_local(const Tensor& meta, int64_t seg_off, int64_t chunk_off, int64_t n_chunks, int64_t dtype,
                 double decay, double neg_lr, double b1, double omb1, double b2, double omb2,
-                const std::optional<Tensor>& gscale) {
+                const std::optional<Tensor>& gscale, int64_t rounding, int64_t rkey, int64_t coord_base) {
   check_dev(meta, "meta");
   TORCH_CHECK(meta.scalar_type() == at::kLong, "dlion: meta must be int64");
+  check_rounding(rounding, dtype, coord_base);
   const c10::DeviceGuard g(meta.device());
   const int64_t* base = meta.data_ptr<int64_t>();
   check_hip(dlion::launch_lion_local(static_cast<int>(dtype), base + seg_off, base + chunk_off, n_chunks,
                                      static_cast<float>(decay), static_cast<float>(neg_lr), static_cast<float>(b1),
                                      static_cast<float>(omb1), static_cast<float>(b2), static_cast<float>(omb2),
-                                     gscale_ptr(gscale), cur_stream()),
+                                     gscale_ptr(gscale), cur_stream(), static_cast<int>(rounding),
+                                     static_cast<uint32_t>(rkey), coord_base),
             "lion_local");
 }
 
@@ -104,8 +113,10 @@ void clip_coef(const Tensor& partial, int64_t n, double max_norm, const Tensor& 
 void lion_vote_apply(const Tensor& meta, int64_t seg_off, int64_t chunk_off, int64_t n_chunks, int64_t dtype,
                      const Tensor& planes, int64_t plane_stride, const Tensor& alive, int64_t mode, int64_t tie,
                      const std::optional<Tensor>& neg, double decay, double neg_lr,
-                     const std::optional<Tensor>& own, const std::optional<Tensor>& agree) {
+                     const std::optional<Tensor>& own, const std::optional<Tensor>& agree, int64_t rounding,
+                     int64_t rkey, int64_t coord_base) {
   check_dev(meta, "meta");
+  check_rounding(rounding, dtype, coord_base);
   check_dev(planes, "planes");
   check_dev(alive, "alive");
   TORCH_CHECK(planes.scalar_type() == at::kByte, "dlion: planes must be uint8");
@@ -141,8 +152,8 @@ void lion_vote_apply(const Tensor& meta, int64_t seg_off, int64_t chunk_off, int
                                           planes.data_ptr<uint8_t>(), plane_stride, alive.data_ptr<uint8_t>(),
                                           static_cast<int>(alive.numel()), static_cast<int>(mode),
                                           static_cast<int>(tie), negp, static_cast<float>(decay),
-                                          static_cast<float>(neg_lr), ownp, agp,
-                                          cur_stream()),
+                                          static_cast<float>(neg_lr), ownp, agp, cur_stream(),
+                                          static_cast<int>(rounding), static_cast<uint32_t>(rkey), coord_base),
             "lion_vote_apply");
 }
 
@@ -1236,7 +1247,8 @@ TORCH_LIBRARY(dlion, m) {
   m.def("softmax_xent_(Tensor(a!) logits, Tensor labels, int v, int variant=0) -> Tensor");
   m.def(
       "lion_local(Tensor meta, int seg_off, int chunk_off, int n_chunks, int dtype, float decay, float neg_lr,"
-      " float b1, float omb1, float b2, float omb2, Tensor? gscale=None) -> ()");
+      " float b1, float omb1, float b2, float omb2, Tensor? gscale=None, int rounding=0, int rkey=0,"
+      " int coord_base=0) -> ()");
   m.def(
       "lion_encode(Tensor meta, int seg_off, int chunk_off, int n_chunks, int dtype, Tensor(a!) bits, float b1,"
       " float omb1, float b2, float omb2, bool update_m, bool stochastic, float rr, int seed, int step,"
@@ -1247,7 +1259,7 @@ TORCH_LIBRARY(dlion, m) {
   m.def(
       "lion_vote_apply(Tensor meta, int seg_off, int chunk_off, int n_chunks, int dtype, Tensor planes,"
       " int plane_stride, Tensor alive, int mode, int tie, Tensor? neg, float decay, float neg_lr,"
-      " Tensor? own, Tensor(b!)? agree) -> ()");
+      " Tensor? own, Tensor(b!)? agree, int rounding=0, int rkey=0, int coord_base=0) -> ()");
   m.def("vote_reduce(Tensor recv, int nbytes, Tensor alive, int tie, Tensor(a!) out, Tensor(b!)? neg_out,"
         " Tensor(c!)? ties=None) -> ()");
   m.def("vote_count(Tensor recv, int nbytes, Tensor alive, Tensor(a!) out, Tensor(b!)? ties) -> ()");

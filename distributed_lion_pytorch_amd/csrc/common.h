@@ -267,6 +267,37 @@ __device__ __forceinline__ uint32_t keep8(uint32_t seed, uint64_t idx, uint32_t 
   return keep4(seed, idx, thresh16) | (keep4(seed, idx + 4, thresh16) << 4);
 }
 
+// ------------------------------------------- stochastic rounding to bf16
+// sr_bf16(x, r), r in [0, 65536): the bf16-representable fp32 value whose
+// upper half is (bits(x) + r) >> 16.  Over uniform r the value rounds away from
+// zero with probability low16(bits(x)) / 65536, so E[result] == x for both
+// signs (sign-magnitude); the carry runs into the exponent (the largest finite
+// value may become Inf), a representable x (+-0 included) comes back unchanged
+// for every r, and NaN / Inf are left to the RNE store.  The oracle is
+// ops/reference.py::sr_bf16.
+__device__ __forceinline__ float sr_bf16(float x, uint32_t r) {
+  const uint32_t u = __float_as_uint(x);
+  if ((u & 0x7f800000u) == 0x7f800000u) return x;
+  return __uint_as_float((u + r) & 0xffff0000u);
+}
+// 32 random bits for the coordinate pair `pair` (= coordinate >> 1) under the
+// launch key rkey (the host's hash of (seed, step), ops/reference.py::sr_key):
+// the low half rounds the even coordinate, the high half the odd one.
+__device__ __forceinline__ uint32_t sr_hash(uint32_t rkey, uint64_t pair) {
+  const uint32_t h = mix32(static_cast<uint32_t>(pair) ^ rkey);
+  return mix32(h + static_cast<uint32_t>(pair >> 32) * 0x9E3779B1u + 0x85EBCA6Bu);
+}
+// the 8 values of a lane, coordinates c .. c + 7 (c % 8 == 0: 4 aligned pairs)
+__device__ __forceinline__ void sr_bf16x8(float (&v)[8], uint32_t rkey, int64_t c) {
+  const uint64_t pair = static_cast<uint64_t>(c) >> 1;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const uint32_t h = sr_hash(rkey, pair + i);
+    v[2 * i] = sr_bf16(v[2 * i], h & 0xffffu);
+    v[2 * i + 1] = sr_bf16(v[2 * i + 1], h >> 16);
+  }
+}
+
 // ------------------------------------------------------------- Philox4x32-10
 // Counter-based RNG for the stochastic-binarization encoder: every
 // (seed, element, step) triple gets an independent, reproducible draw.

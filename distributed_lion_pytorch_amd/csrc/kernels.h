@@ -8,9 +8,11 @@
 namespace dlion {
 
 // ---- optimizer (lion_kernels.hip)
+// rounding (K0 and K2): 0 = round to nearest even, 1 = stochastic rounding of the bf16 parameter store with
+// the 16 hash bits of (rkey, cbase + bit_off + e) per element; cbase = 8 * the bucket's byte offset
 hipError_t launch_lion_local(int dt, const int64_t* seg, const int64_t* chunks, int64_t n_chunks, float decay,
                              float neg_lr, float b1, float omb1, float b2, float omb2, const float* gscale,
-                             hipStream_t st);
+                             hipStream_t st, int rounding = 0, uint32_t rkey = 0, int64_t cbase = 0);
 hipError_t launch_lion_encode(int dt, const int64_t* seg, const int64_t* chunks, int64_t n_chunks, uint8_t* bits,
                               float b1, float omb1, float b2, float omb2, int update_m, int stochastic, float rr,
                               uint64_t seed, uint32_t step, const float* gscale, hipStream_t st);
@@ -21,7 +23,8 @@ hipError_t launch_clip_coef(const float* partial, int64_t n, float max_norm, flo
 hipError_t launch_lion_vote_apply(int dt, const int64_t* seg, const int64_t* chunks, int64_t n_chunks,
                                   const uint8_t* planes, int64_t plane_stride, const uint8_t* alive, int world,
                                   int mode, int tie, const uint8_t* neg, float decay, float neg_lr, const uint8_t* own,
-                                  unsigned long long* agree, hipStream_t st);
+                                  unsigned long long* agree, hipStream_t st, int rounding = 0, uint32_t rkey = 0,
+                                  int64_t cbase = 0);
 hipError_t launch_vote_reduce(const uint8_t* recv, int64_t nbytes, const uint8_t* alive, int world, int tie,
                               uint8_t* out, uint8_t* neg_out, unsigned long long* ties, hipStream_t st);
 // average vote on the all-to-all path: out[P][nbytes] = bit planes of the live-voter count, P = bit_length(world)

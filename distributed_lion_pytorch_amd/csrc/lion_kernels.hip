@@ -110,12 +110,35 @@ __device__ __forceinline__ void clip8(float (&gv)[8], float cs) {
   for (int j = 0; j < 8; ++j) gv[j] = Elem<DT>::rnd(gv[j] * cs);
 }
 
+// Parameter store rounding (SR instantiations, bf16 parameters only; the
+// default SR = false is round-to-nearest-even after each of the two ATen ops,
+// the reference's arithmetic).  Stochastic: the decayed parameter stays an
+// unrounded fp32 product, x = fma(-lr, delta, p * decay) is rounded ONCE, to a
+// bf16 neighbour chosen by sr_bf16 with the coordinate's 16 hash bits -- on
+// purpose not the nearest path's two roundings: with a single unbiased
+// rounding both the weight decay and the step survive in expectation, where
+// nearest drops a step below half an ulp (every |p| >= 2^-5 at lr 1e-4) and
+// every decay of 1 - 1e-5.  The value handed to store8 / store8g is then
+// representable, so their RNE conversion is exact.  The coordinate of element
+// e of a segment is cbase + bit_off + e with cbase = 8 * the bucket's byte
+// offset: unique across the plan and the same on every rank, as is rkey, so
+// replicas round identically.  The momentum keeps its RNE stores.
+template <int DT, bool SR>
+__device__ __forceinline__ float decayed(float p, float decay) {
+  if constexpr (SR) return p * decay;
+  else return Elem<DT>::rnd(p * decay);
+}
+template <bool SR>
+__device__ __forceinline__ void sr_round8(float (&v)[8], uint32_t rkey, int64_t coord) {
+  if constexpr (SR) sr_bf16x8(v, rkey, coord);
+}
+
 // ----------------------------------------------------------------------- K0
-template <int DT>
+template <int DT, bool SR>
 __global__ void __launch_bounds__(kThreads)
 lion_local_kernel(const int64_t* __restrict__ seg, const int64_t* __restrict__ chunks,
                   float decay, float neg_lr, float b1, float omb1, float b2, float omb2,
-                  const float* __restrict__ gscale) {
+                  const float* __restrict__ gscale, uint32_t rkey, int64_t cbase) {
   using E = Elem<DT>;
   using S = typename E::S;
   const int64_t s = chunks[2 * blockIdx.x], start = chunks[2 * blockIdx.x + 1];
@@ -143,11 +166,12 @@ lion_local_kernel(const int64_t* __restrict__ seg, const int64_t* __restrict__ c
       if (gscale != nullptr) clip8<DT>(gv, cs);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        const float pw = E::rnd(pv[j] * decay);
+        const float pw = decayed<DT, SR>(pv[j], decay);
         const float u = E::rnd(__fmaf_rn(gv[j], omb1, E::rnd(mv[j] * b1)));
         pv[j] = __fmaf_rn(neg_lr, sgn(u), pw);
         mv[j] = __fmaf_rn(gv[j], omb2, E::rnd(mv[j] * b2));
       }
+      sr_round8<SR>(pv, rkey, cbase + r.bit_off + e);
       E::store8(p + e, pv);
       E::store8(m + e, mv);
     }
@@ -164,11 +188,12 @@ lion_local_kernel(const int64_t* __restrict__ seg, const int64_t* __restrict__ c
     if (gscale != nullptr) clip8<DT>(gv, cs);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const float pw = E::rnd(pv[j] * decay);                       // p *= 1 - lr*wd
+      const float pw = decayed<DT, SR>(pv[j], decay);               // p *= 1 - lr*wd
       const float u = E::rnd(__fmaf_rn(gv[j], omb1, E::rnd(mv[j] * b1)));  // b1*m + (1-b1)*g
       pv[j] = __fmaf_rn(neg_lr, sgn(u), pw);                         // p -= lr*sign(u)
       mv[j] = __fmaf_rn(gv[j], omb2, E::rnd(mv[j] * b2));            // m = b2*m + (1-b2)*g
     }
+    sr_round8<SR>(pv, rkey, cbase + r.bit_off + e);
     store8g<DT>(p, e, r.n, r.vec, pv);
     store8g<DT>(m, e, r.n, r.vec, mv);
   }
@@ -294,13 +319,14 @@ lion_encode_kernel(const int64_t* __restrict__ seg, const int64_t* __restrict__ 
 // p <- round(round(p * decay) - lr * delta)   (ref :64 then :92)
 // agree (optional): count of coordinates where this rank's own bits (`own`,
 // its send plane) agree with the voted direction (vote-agreement telemetry).
-template <int DT>
+template <int DT, bool SR>
 __global__ void __launch_bounds__(kThreads)
 lion_vote_apply_kernel(const int64_t* __restrict__ seg, const int64_t* __restrict__ chunks,
                        const uint8_t* __restrict__ planes, int64_t plane_stride,
                        const uint8_t* __restrict__ alive, int world, int mode, int tie,
                        const uint8_t* __restrict__ neg, float decay, float neg_lr,
-                       const uint8_t* __restrict__ own, unsigned long long* __restrict__ agree) {
+                       const uint8_t* __restrict__ own, unsigned long long* __restrict__ agree, uint32_t rkey,
+                       int64_t cbase) {
   using E = Elem<DT>;
   using S = typename E::S;
   const int64_t s = chunks[2 * blockIdx.x], start = chunks[2 * blockIdx.x + 1];
@@ -354,7 +380,8 @@ lion_vote_apply_kernel(const int64_t* __restrict__ seg, const int64_t* __restric
     float pv[8];
     load8g<DT>(p, e, r.n, r.vec, pv);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) pv[j] = __fmaf_rn(neg_lr, delta[j], E::rnd(pv[j] * decay));
+    for (int j = 0; j < 8; ++j) pv[j] = __fmaf_rn(neg_lr, delta[j], decayed<DT, SR>(pv[j], decay));
+    sr_round8<SR>(pv, rkey, cbase + r.bit_off + e);
     store8g<DT>(p, e, r.n, r.vec, pv);
   }
   if (agree != nullptr) {
@@ -434,13 +461,14 @@ __device__ __forceinline__ void sliced_vote(const uint32_t (&w)[kMaxSliced], int
   }
 }
 
-template <int DT>
+template <int DT, bool SR>
 __global__ void __launch_bounds__(kThreads)
 lion_vote_apply32_kernel(const int64_t* __restrict__ seg, const int64_t* __restrict__ chunks,
                          const uint8_t* __restrict__ planes, int64_t plane_stride,
                          const uint8_t* __restrict__ alive, int world, int mode, int tie,
                          const uint8_t* __restrict__ neg_plane, float decay, float neg_lr,
-                         const uint8_t* __restrict__ own, unsigned long long* __restrict__ agree) {
+                         const uint8_t* __restrict__ own, unsigned long long* __restrict__ agree, uint32_t rkey,
+                         int64_t cbase) {
   using E = Elem<DT>;
   using S = typename E::S;
   const int64_t s = chunks[2 * blockIdx.x], start = chunks[2 * blockIdx.x + 1];
@@ -496,8 +524,9 @@ lion_vote_apply32_kernel(const int64_t* __restrict__ seg, const int64_t* __restr
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const float delta = static_cast<float>(static_cast<int>((pos >> j) & 1) - static_cast<int>((neg >> j) & 1));
-        pv[j] = __fmaf_rn(neg_lr, delta, E::rnd(pv[j] * decay));
+        pv[j] = __fmaf_rn(neg_lr, delta, decayed<DT, SR>(pv[j], decay));
       }
+      sr_round8<SR>(pv, rkey, cbase + r.bit_off + e);
       E::store8(p + e, pv);
     }
     return;
@@ -532,8 +561,9 @@ lion_vote_apply32_kernel(const int64_t* __restrict__ seg, const int64_t* __restr
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const float delta = static_cast<float>(static_cast<int>((pos >> j) & 1) - static_cast<int>((neg >> j) & 1));
-      pv[j] = __fmaf_rn(neg_lr, delta, E::rnd(pv[j] * decay));
+      pv[j] = __fmaf_rn(neg_lr, delta, decayed<DT, SR>(pv[j], decay));
     }
+    sr_round8<SR>(pv, rkey, cbase + r.bit_off + e);
     store8g<DT>(p, e, r.n, r.vec, pv);
   }
   if (agree != nullptr) {
@@ -569,28 +599,37 @@ template <bool MAJ>
 __device__ __forceinline__ void vote_word(const VoteCtx& v, int64_t word, uint32_t& pos, uint32_t& neg) {
   if constexpr (MAJ) {
     uint32_t w[kMaxSliced], tb;
+    // Opaque copies of the live mask and count for this word: with the
+    // originals the compiler hoists every "plane k is live" and "bit b of
+    // n_live / 2" test out of the block's 8 unrolled votes and keeps each as a
+    // 64-bit lane mask (plus its negation) -- 70-96 SGPRs spilled into VGPR
+    // lanes and read back around every plane load.  A copy per call is tested
+    // where it is used (s_bitcmp + branch): no spill.
+    uint32_t lm = v.live_mask;
+    int nl = v.n_live;
+    asm volatile("" : "+s"(lm), "+s"(nl));
 #pragma unroll
     for (int k = 0; k < kMaxSliced; ++k)
-      w[k] = (v.live_mask >> k) & 1 ? reinterpret_cast<const uint32_t*>(v.planes + k * v.plane_stride)[word] : 0u;
-    sliced_vote(w, v.world, v.n_live, v.tie, pos, neg, tb);
+      w[k] = (lm >> k) & 1 ? reinterpret_cast<const uint32_t*>(v.planes + k * v.plane_stride)[word] : 0u;
+    sliced_vote(w, v.world, nl, v.tie, pos, neg, tb);
   } else {
     pos = reinterpret_cast<const uint32_t*>(v.planes)[word];
     neg = v.neg_plane ? reinterpret_cast<const uint32_t*>(v.neg_plane)[word] : ~pos;
   }
 }
 
-template <int DT>
+template <int DT, bool SR>
 __device__ __forceinline__ void apply8(float (&pv)[8], uint32_t pos, uint32_t neg, float decay, float neg_lr) {
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     const float delta = static_cast<float>(static_cast<int>((pos >> j) & 1) - static_cast<int>((neg >> j) & 1));
-    pv[j] = __fmaf_rn(neg_lr, delta, Elem<DT>::rnd(pv[j] * decay));
+    pv[j] = __fmaf_rn(neg_lr, delta, decayed<DT, SR>(pv[j], decay));
   }
 }
 
-template <int DT, bool MAJ>
+template <int DT, bool MAJ, bool SR>
 __device__ __forceinline__ void apply_chunk(const SegRow& r, int64_t start, const VoteCtx& v, float decay,
-                                            float neg_lr) {
+                                            float neg_lr, uint32_t rkey, int64_t cbase) {
   using S = typename Elem<DT>::S;
   S* p = const_cast<S*>(static_cast<const S*>(r.p));
   const int sub = threadIdx.x & 3;
@@ -602,16 +641,18 @@ __device__ __forceinline__ void apply_chunk(const SegRow& r, int64_t start, cons
     vote_word<MAJ>(v, (r.bit_off + e) >> 5, pos, neg);
     float pv[8];
     load8g<DT>(p, e, r.n, r.vec, pv);
-    apply8<DT>(pv, (pos >> (8 * sub)) & 0xffu, (neg >> (8 * sub)) & 0xffu, decay, neg_lr);
+    apply8<DT, SR>(pv, (pos >> (8 * sub)) & 0xffu, (neg >> (8 * sub)) & 0xffu, decay, neg_lr);
+    sr_round8<SR>(pv, rkey, cbase + r.bit_off + e);
     store8g<DT>(p, e, r.n, r.vec, pv);
   }
 }
 
-template <int DT, bool MAJ, int CPB>
+template <int DT, bool MAJ, int CPB, bool SR>
 __global__ void __launch_bounds__(kThreads)
 lion_apply_pair_kernel(const int64_t* __restrict__ seg, const int64_t* __restrict__ chunks, int64_t n_chunks,
                        const uint8_t* __restrict__ planes, int64_t plane_stride, const uint8_t* __restrict__ alive,
-                       int world, int tie, const uint8_t* __restrict__ neg_plane, float decay, float neg_lr) {
+                       int world, int tie, const uint8_t* __restrict__ neg_plane, float decay, float neg_lr,
+                       uint32_t rkey, int64_t cbase) {
   using E = Elem<DT>;
   using S = typename E::S;
   // CPB chunks per block (kPairChunks): every chunk's metadata chain is in
@@ -661,14 +702,15 @@ lion_apply_pair_kernel(const int64_t* __restrict__ seg, const int64_t* __restric
       if constexpr (MAJ) vote_word<true>(v, (rs[c].bit_off + e) >> 5, pw[q], nw[q]);
       float pv[8];
       rp[q].unpack(pv);
-      apply8<DT>(pv, (pw[q] >> (8 * sub)) & 0xffu, (nw[q] >> (8 * sub)) & 0xffu, decay, neg_lr);
+      apply8<DT, SR>(pv, (pw[q] >> (8 * sub)) & 0xffu, (nw[q] >> (8 * sub)) & 0xffu, decay, neg_lr);
+      sr_round8<SR>(pv, rkey, cbase + rs[c].bit_off + e);
       E::store8(const_cast<S*>(static_cast<const S*>(rs[c].p)) + e, pv);
     }
     return;
   }
 #pragma unroll
   for (int c = 0; c < CPB; ++c)
-    if (has[c]) apply_chunk<DT, MAJ>(rs[c], st[c], v, decay, neg_lr);
+    if (has[c]) apply_chunk<DT, MAJ, SR>(rs[c], st[c], v, decay, neg_lr, rkey, cbase);
 }
 
 // ------------------------------------------------------- K2, counted (mode 3)
@@ -756,15 +798,16 @@ __device__ __forceinline__ void counted_delta8(const uint32_t (&cw)[kMaxCountPla
   }
 }
 
-template <int DT>
+template <int DT, bool SR>
 __device__ __forceinline__ void apply8_delta(float (&pv)[8], const float (&delta)[8], float decay, float neg_lr) {
 #pragma unroll
-  for (int j = 0; j < 8; ++j) pv[j] = __fmaf_rn(neg_lr, delta[j], Elem<DT>::rnd(pv[j] * decay));
+  for (int j = 0; j < 8; ++j) pv[j] = __fmaf_rn(neg_lr, delta[j], decayed<DT, SR>(pv[j], decay));
 }
 
-template <int DT, bool TEL>
+template <int DT, bool TEL, bool SR>
 __device__ __forceinline__ void counted_chunk(const SegRow& r, int64_t start, const CountCtx& v, float decay,
-                                              float neg_lr, const uint8_t* __restrict__ own, uint32_t& n_agree) {
+                                              float neg_lr, const uint8_t* __restrict__ own, uint32_t& n_agree,
+                                              uint32_t rkey, int64_t cbase) {
   using S = typename Elem<DT>::S;
   S* p = const_cast<S*>(static_cast<const S*>(r.p));
   SpanPos sp = span_pos((r.bit_off + start) >> 3, v.shard);
@@ -784,7 +827,8 @@ __device__ __forceinline__ void counted_chunk(const SegRow& r, int64_t start, co
         if (e + j < r.n) n_agree += (((mine >> j) & 1) ? 1.f : -1.f) * delta[j] > 0.f;
     }
     load8g<DT>(p, e, r.n, r.vec, pv);
-    apply8_delta<DT>(pv, delta, decay, neg_lr);
+    apply8_delta<DT, SR>(pv, delta, decay, neg_lr);
+    sr_round8<SR>(pv, rkey, cbase + r.bit_off + e);
     store8g<DT>(p, e, r.n, r.vec, pv);
   }
 }
@@ -794,12 +838,12 @@ __device__ __forceinline__ void counted_chunk(const SegRow& r, int64_t start, co
 // plane words (at most 8 x 4 dwords + 8 Raw8) are loaded before the first use.
 // With telemetry (TEL, CPB = 1): agree[0] += #(own sign * delta > 0); the ties
 // were counted by K4c on the shard, as in the pre-voted path.
-template <int DT, int CPB, bool TEL>
+template <int DT, int CPB, bool TEL, bool SR>
 __global__ void __launch_bounds__(kThreads)
 lion_apply_counted_kernel(const int64_t* __restrict__ seg, const int64_t* __restrict__ chunks, int64_t n_chunks,
                           const uint8_t* __restrict__ planes, int64_t shard, const uint8_t* __restrict__ alive,
                           int world, float decay, float neg_lr, const uint8_t* __restrict__ own,
-                          unsigned long long* __restrict__ agree) {
+                          unsigned long long* __restrict__ agree, uint32_t rkey, int64_t cbase) {
   using E = Elem<DT>;
   using S = typename E::S;
   const int64_t c0 = CPB * static_cast<int64_t>(blockIdx.x);
@@ -843,7 +887,8 @@ lion_apply_counted_kernel(const int64_t* __restrict__ seg, const int64_t* __rest
         float delta[8], pv[8];
         counted_delta8(cw[q], v, delta);
         rp[q].unpack(pv);
-        apply8_delta<DT>(pv, delta, decay, neg_lr);
+        apply8_delta<DT, SR>(pv, delta, decay, neg_lr);
+        sr_round8<SR>(pv, rkey, cbase + rs[c].bit_off + e);
         E::store8(const_cast<S*>(static_cast<const S*>(rs[c].p)) + e, pv);
       }
       return;
@@ -852,7 +897,7 @@ lion_apply_counted_kernel(const int64_t* __restrict__ seg, const int64_t* __rest
   uint32_t n_agree = 0;
 #pragma unroll
   for (int c = 0; c < CPB; ++c)
-    if (has[c]) counted_chunk<DT, TEL>(rs[c], st[c], v, decay, neg_lr, own, n_agree);
+    if (has[c]) counted_chunk<DT, TEL, SR>(rs[c], st[c], v, decay, neg_lr, own, n_agree, rkey, cbase);
   if constexpr (TEL) {
     for (int off = 32; off > 0; off >>= 1) n_agree += __shfl_xor(n_agree, off);
     if ((threadIdx.x & 63) == 0) atomicAdd(agree, static_cast<unsigned long long>(n_agree));
@@ -1096,12 +1141,29 @@ __global__ void __launch_bounds__(1024) clip_coef_kernel(const float* __restrict
     default: return hipErrorInvalidValue;               \
   }
 
+// Parameter store rounding of K0 / K2: 0 = nearest (default), 1 = stochastic.
+// Stochastic applies to bf16 parameters (the SR instantiations); an fp32 store
+// is exact already, so there the mode runs the nearest kernels; fp16 is refused.
+#define DLION_DISPATCH_SR(dt, sr, ...)    \
+  if (sr) {                               \
+    constexpr int DT = kBF16;             \
+    constexpr bool SR = true;             \
+    __VA_ARGS__;                          \
+  } else {                                \
+    constexpr bool SR = false;            \
+    DLION_DISPATCH(dt, __VA_ARGS__)       \
+  }
+
+static bool rounding_ok(int dt, int rounding) { return rounding == 0 || (rounding == 1 && dt != kF16); }
+
 hipError_t launch_lion_local(int dt, const int64_t* seg, const int64_t* chunks, int64_t n_chunks,
                              float decay, float neg_lr, float b1, float omb1, float b2, float omb2,
-                             const float* gscale, hipStream_t st) {
+                             const float* gscale, hipStream_t st, int rounding, uint32_t rkey, int64_t cbase) {
+  if (!rounding_ok(dt, rounding)) return hipErrorInvalidValue;
   if (n_chunks == 0) return hipSuccess;
-  DLION_DISPATCH(dt, hipLaunchKernelGGL((lion_local_kernel<DT>), dim3(n_chunks), dim3(kThreads), 0, st,
-                                        seg, chunks, decay, neg_lr, b1, omb1, b2, omb2, gscale));
+  const bool sr = rounding == 1 && dt == kBF16;
+  DLION_DISPATCH_SR(dt, sr, hipLaunchKernelGGL((lion_local_kernel<DT, SR>), dim3(n_chunks), dim3(kThreads), 0, st,
+                                               seg, chunks, decay, neg_lr, b1, omb1, b2, omb2, gscale, rkey, cbase));
   return hipGetLastError();
 }
 
@@ -1124,44 +1186,47 @@ hipError_t launch_lion_encode(int dt, const int64_t* seg, const int64_t* chunks,
 hipError_t launch_lion_vote_apply(int dt, const int64_t* seg, const int64_t* chunks, int64_t n_chunks,
                                   const uint8_t* planes, int64_t plane_stride, const uint8_t* alive, int world,
                                   int mode, int tie, const uint8_t* neg, float decay, float neg_lr,
-                                  const uint8_t* own, unsigned long long* agree, hipStream_t st) {
+                                  const uint8_t* own, unsigned long long* agree, hipStream_t st, int rounding,
+                                  uint32_t rkey, int64_t cbase) {
+  if (!rounding_ok(dt, rounding)) return hipErrorInvalidValue;
   if (n_chunks == 0) return hipSuccess;
+  const bool sr = rounding == 1 && dt == kBF16;
+  const dim3 pairs((n_chunks + kPairChunks - 1) / kPairChunks), each(n_chunks), thr(kThreads);
   if (mode == 3) {  // counted: planes[W][P][shard], plane_stride = shard
     if (world < 1 || world > kMaxSliced || plane_stride <= 0 || plane_stride % (kSpan / 8) != 0)
       return hipErrorInvalidValue;
     if (agree == nullptr) {
-      DLION_DISPATCH(dt, hipLaunchKernelGGL((lion_apply_counted_kernel<DT, kPairChunks, false>),
-                                            dim3((n_chunks + kPairChunks - 1) / kPairChunks), dim3(kThreads), 0, st, seg,
-                                            chunks, n_chunks, planes, plane_stride, alive, world, decay, neg_lr, own,
-                                            agree));
+      DLION_DISPATCH_SR(dt, sr, hipLaunchKernelGGL((lion_apply_counted_kernel<DT, kPairChunks, false, SR>), pairs, thr,
+                                                   0, st, seg, chunks, n_chunks, planes, plane_stride, alive, world,
+                                                   decay, neg_lr, own, agree, rkey, cbase));
     } else {
-      DLION_DISPATCH(dt, hipLaunchKernelGGL((lion_apply_counted_kernel<DT, 1, true>), dim3(n_chunks), dim3(kThreads), 0,
-                                            st, seg, chunks, n_chunks, planes, plane_stride, alive, world, decay, neg_lr,
-                                            own, agree));
+      DLION_DISPATCH_SR(dt, sr, hipLaunchKernelGGL((lion_apply_counted_kernel<DT, 1, true, SR>), each, thr, 0, st, seg,
+                                                   chunks, n_chunks, planes, plane_stride, alive, world, decay, neg_lr,
+                                                   own, agree, rkey, cbase));
     }
     return hipGetLastError();
   }
   if (mode == 2 && agree == nullptr) {
-    DLION_DISPATCH(dt, hipLaunchKernelGGL((lion_apply_pair_kernel<DT, false, kPairChunks>), dim3((n_chunks + kPairChunks - 1) / kPairChunks),
-                                          dim3(kThreads), 0, st, seg, chunks, n_chunks, planes, plane_stride, alive,
-                                          world, tie, neg, decay, neg_lr));
+    DLION_DISPATCH_SR(dt, sr, hipLaunchKernelGGL((lion_apply_pair_kernel<DT, false, kPairChunks, SR>), pairs, thr, 0,
+                                                 st, seg, chunks, n_chunks, planes, plane_stride, alive, world, tie,
+                                                 neg, decay, neg_lr, rkey, cbase));
     return hipGetLastError();
   }
   if (mode == 0 && world <= kMaxSliced && agree == nullptr) {
-    DLION_DISPATCH(dt, hipLaunchKernelGGL((lion_apply_pair_kernel<DT, true, kPairChunks>), dim3((n_chunks + kPairChunks - 1) / kPairChunks),
-                                          dim3(kThreads), 0, st, seg, chunks, n_chunks, planes, plane_stride, alive,
-                                          world, tie, neg, decay, neg_lr));
+    DLION_DISPATCH_SR(dt, sr, hipLaunchKernelGGL((lion_apply_pair_kernel<DT, true, kPairChunks, SR>), pairs, thr, 0,
+                                                 st, seg, chunks, n_chunks, planes, plane_stride, alive, world, tie,
+                                                 neg, decay, neg_lr, rkey, cbase));
     return hipGetLastError();
   }
   if (mode == 2 || (mode == 0 && world <= kMaxSliced)) {
-    DLION_DISPATCH(dt, hipLaunchKernelGGL((lion_vote_apply32_kernel<DT>), dim3(n_chunks), dim3(kThreads), 0, st,
-                                          seg, chunks, planes, plane_stride, alive, world, mode, tie, neg, decay,
-                                          neg_lr, own, agree));
+    DLION_DISPATCH_SR(dt, sr, hipLaunchKernelGGL((lion_vote_apply32_kernel<DT, SR>), each, thr, 0, st, seg, chunks,
+                                                 planes, plane_stride, alive, world, mode, tie, neg, decay, neg_lr,
+                                                 own, agree, rkey, cbase));
     return hipGetLastError();
   }
-  DLION_DISPATCH(dt, hipLaunchKernelGGL((lion_vote_apply_kernel<DT>), dim3(n_chunks), dim3(kThreads), 0, st,
-                                        seg, chunks, planes, plane_stride, alive, world, mode, tie, neg, decay,
-                                        neg_lr, own, agree));
+  DLION_DISPATCH_SR(dt, sr, hipLaunchKernelGGL((lion_vote_apply_kernel<DT, SR>), each, thr, 0, st, seg, chunks, planes,
+                                               plane_stride, alive, world, mode, tie, neg, decay, neg_lr, own, agree,
+                                               rkey, cbase));
   return hipGetLastError();
 }
 

@@ -204,17 +204,129 @@ def vote_reduce_bits(planes_bits: torch.Tensor, alive: torch.Tensor, tie: int):
     return pos, neg
 
 
-def apply_delta_(p: torch.Tensor, delta: torch.Tensor, lr: float, wd: float) -> None:
-    """p <- round(round(p*(1-lr*wd)) - lr*delta)  (ref :64 then :92)."""
+# ------------------------------------------------- stochastic rounding
+# Opt-in rounding of the bf16 parameter store (Lion(param_rounding="stochastic")).
+# Round-to-nearest drops every update below half a bf16 ulp: at lr 1e-4 no
+# weight with |p| >= 2^-5 moves, and a decay of 1 - 1e-5 never does.  The
+# stochastic store picks one of the two bf16 neighbours of the fp32 result
+# with probability proportional to the remainder, so E[stored] == the fp32
+# value.  The 16 random bits of a coordinate are a pure integer hash of
+# (seed, step, global coordinate) -- the same on every rank, reproduced here
+# with int64 arithmetic masked to 32 bits (csrc/common.h: sr_bf16, sr_hash).
+ROUND_NEAREST = 0
+ROUND_STOCHASTIC = 1
+ROUNDING_CODES = {"nearest": ROUND_NEAREST, "stochastic": ROUND_STOCHASTIC}
+
+_M32 = 0xFFFFFFFF
+
+
+def _mix32(x):
+    """The lowbias32 finaliser on a Python int or an int64 tensor of 32-bit values."""
+    x = x ^ (x >> 16)
+    x = (x * 0x7FEB352D) & _M32
+    x = x ^ (x >> 15)
+    x = (x * 0x846CA68B) & _M32
+    return x ^ (x >> 16)
+
+
+def sr_key(seed: int, step: int) -> int:
+    """The 32-bit launch key that folds (seed, step): one per optimizer step,
+    computed on the host, identical on every rank (no rank term)."""
+    seed, step = int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF
+    k = _mix32((seed & _M32) ^ 0x9E3779B9)
+    k = _mix32(k ^ (seed >> 32))
+    k = _mix32((k + (step & _M32)) & _M32)
+    return _mix32(k ^ (step >> 32))
+
+
+def sr_bits16(coords: torch.Tensor, seed: int, step: int) -> torch.Tensor:
+    """int64 r in [0, 65536) for each global coordinate (int64 tensor).  One
+    32-bit hash per coordinate pair ``c >> 1``: mix32(mix32(lo32(pair) ^ key)
+    + hi32(pair) * 0x9E3779B1 + 0x85EBCA6B); the low half belongs to the even
+    coordinate, the high half to the odd one."""
+    c = coords.to(torch.int64)
+    pair = c >> 1
+    h = _mix32((pair & _M32) ^ sr_key(seed, step))
+    h = _mix32((h + ((pair >> 32) & _M32) * 0x9E3779B1 + 0x85EBCA6B) & _M32)
+    return (h >> ((c & 1) * 16)) & 0xFFFF
+
+
+def sr_bf16(x: torch.Tensor, r: torch.Tensor) -> torch.Tensor:
+    """fp32 ``x``, int64 ``r`` in [0, 65536) -> the bfloat16 whose bit pattern
+    is ``(bits(x) + r) >> 16``: it rounds away from zero with probability
+    low16(bits(x)) / 65536 over uniform r (unbiased for both signs), a
+    representable x is unchanged for every r, the carry runs into the exponent
+    (the largest finite value may become Inf); NaN and Inf round to nearest."""
+    assert x.dtype == torch.float32
+    bits = x.contiguous().view(torch.int32).to(torch.int64) & _M32
+    out = (bits + r.to(torch.int64).view(x.shape)) & 0xFFFF0000
+    out = torch.where(out >= 1 << 31, out - (1 << 32), out).to(torch.int32).view(torch.float32)
+    return torch.where(torch.isfinite(x), out, x).to(torch.bfloat16)
+
+
+def _fma32(a: float, b: torch.Tensor, c: torch.Tensor) -> torch.Tensor:
+    """fp32 fma(a, b, c), correctly rounded, for fp32 tensors b and c and a
+    scalar a (rounded to fp32): the product is exact in fp64; the fp64 sum is
+    turned into its round-to-odd value (TwoSum error -> sticky bit), after
+    which the rounding to fp32 cannot double-round."""
+    a64 = torch.tensor(a, dtype=torch.float32, device=b.device).double()
+    prod, c64 = a64 * b.double(), c.double()
+    s = prod + c64
+    t = s - prod
+    err = (prod - (s - t)) + (c64 - t)
+    sb = s.view(torch.int64)
+    inexact = (err != 0) & torch.isfinite(s)
+    toward_zero = inexact & ((err > 0) != (s > 0))  # |exact| < |s|: truncate by one ulp first
+    odd = (sb - toward_zero.to(torch.int64)) | 1
+    return torch.where(inexact, odd, sb).view(torch.float64).float()
+
+
+def sr_bf16_(p: torch.Tensor, x: torch.Tensor, coords: torch.Tensor, seed: int, step: int) -> None:
+    """Store fp32 ``x`` into the bf16 parameter ``p`` with the stochastic
+    rounding of its coordinates under (seed, step)."""
+    p.copy_(sr_bf16(x.reshape(-1), sr_bits16(coords, seed, step)).view(p.shape))
+
+
+def _apply_stochastic_(p, delta, lr, wd, coords, seed, step) -> None:
+    # ONE rounding: x = fma(-lr, delta, p * decay) with the decayed parameter
+    # kept as an fp32 product -- on purpose not the nearest path's two bf16
+    # roundings, so that both the decay and the step survive in expectation
+    decay = torch.tensor(1 - lr * wd, dtype=torch.float32, device=p.device)
+    x = _fma32(-lr, delta.reshape(-1).float(), p.reshape(-1).float() * decay)
+    sr_bf16_(p, x, coords, seed, step)
+
+
+def _stochastic(p: torch.Tensor, rounding: int) -> bool:
+    if rounding not in (ROUND_NEAREST, ROUND_STOCHASTIC):
+        raise ValueError(f"rounding must be one of {tuple(ROUNDING_CODES.values())}")
+    if rounding == ROUND_STOCHASTIC and p.dtype == torch.float16:
+        raise ValueError("stochastic parameter rounding supports bfloat16 (and is a no-op for float32), not float16")
+    return rounding == ROUND_STOCHASTIC and p.dtype == torch.bfloat16  # an fp32 store is exact: nearest
+
+
+def apply_delta_(p: torch.Tensor, delta: torch.Tensor, lr: float, wd: float, rounding: int = ROUND_NEAREST,
+                 coords: Optional[torch.Tensor] = None, seed: int = 0, step: int = 0) -> None:
+    """p <- round(round(p*(1-lr*wd)) - lr*delta)  (ref :64 then :92).
+
+    ``rounding=ROUND_STOCHASTIC`` (bf16 p): p <- sr_bf16(fma(-lr, delta,
+    p*(1-lr*wd))) with the bits of ``coords`` (the elements' global
+    coordinates, int64) under ``(seed, step)``."""
+    if _stochastic(p, rounding):
+        return _apply_stochastic_(p, delta, lr, wd, coords, seed, step)
     p.mul_(1 - lr * wd)
     p.add_(delta.view(p.shape), alpha=-lr)
 
 
 # ------------------------------------------- reference-compatible functions
-def update_fn(p, grad, exp_avg, lr, wd, beta1, beta2) -> None:
-    """Single-node Lion step (ref :47-59); sign(0) leaves the coordinate."""
-    p.mul_(1 - lr * wd)
-    p.add_(interp(grad, exp_avg, beta1).sign_(), alpha=-lr)
+def update_fn(p, grad, exp_avg, lr, wd, beta1, beta2, rounding: int = ROUND_NEAREST,
+              coords: Optional[torch.Tensor] = None, seed: int = 0, step: int = 0) -> None:
+    """Single-node Lion step (ref :47-59); sign(0) leaves the coordinate.
+    ``rounding`` / ``coords`` / ``seed`` / ``step``: as in :func:`apply_delta_`."""
+    if _stochastic(p, rounding):
+        _apply_stochastic_(p, interp(grad, exp_avg, beta1).sign_(), lr, wd, coords, seed, step)
+    else:
+        p.mul_(1 - lr * wd)
+        p.add_(interp(grad, exp_avg, beta1).sign_(), alpha=-lr)
     momentum_update_(grad, exp_avg, beta2)
 
 

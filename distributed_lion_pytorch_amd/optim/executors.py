@@ -33,6 +33,25 @@ def _region_bytes(numel: int) -> int:
     return (numel + ALIGN_ELEMS - 1) // ALIGN_ELEMS * ALIGN_ELEMS // 8
 
 
+def coord_base(b: Bucket) -> int:
+    """Global coordinate of the bucket's first bit: element e of segment s has
+    the coordinate ``coord_base(b) + s.bit_off + e``, unique across the plan
+    and the same on every rank (what the stochastic parameter rounding hashes)."""
+    return 8 * b.byte_off
+
+
+def _rounding_args(b: Bucket, rounding: int, seed: int, step: int):
+    """Trailing (rounding, rkey, coord_base) arguments of the K0 / K2 ops;
+    none for nearest, the ops' default."""
+    if rounding == ref.ROUND_NEAREST:
+        return ()
+    return rounding, ref.sr_key(seed, step), coord_base(b)
+
+
+def _coords(b: Bucket, s) -> torch.Tensor:
+    return coord_base(b) + s.bit_off + torch.arange(s.numel, dtype=torch.int64, device=s.param.device)
+
+
 class HipExecutor:
     name = "hip"
 
@@ -43,9 +62,11 @@ class HipExecutor:
     def _chunk_off(self, b: Bucket) -> int:
         return self.plan.chunk_off + 2 * b.chunk_off
 
-    def local(self, meta, b: Bucket, hp: HParams, grads=None, moms=None, gscale=None) -> None:
+    def local(self, meta, b: Bucket, hp: HParams, grads=None, moms=None, gscale=None,
+              rounding: int = ref.ROUND_NEAREST, seed: int = 0, step: int = 0) -> None:
         self.ops.lion_local(meta, self.plan.seg_off, self._chunk_off(b), b.n_chunks, hip.DTYPE_CODE[b.dtype],
-                            hp.decay, -hp.lr, hp.beta1, 1.0 - hp.beta1, hp.beta2, 1.0 - hp.beta2, gscale)
+                            hp.decay, -hp.lr, hp.beta1, 1.0 - hp.beta1, hp.beta2, 1.0 - hp.beta2, gscale,
+                            *_rounding_args(b, rounding, seed, step))
 
     def encode(self, meta, b: Bucket, bits: torch.Tensor, hp: HParams, update_m: bool = True,
                stochastic: bool = False, rr: float = 0.0, seed: int = 0, step: int = 0,
@@ -64,9 +85,11 @@ class HipExecutor:
 
     def apply(self, meta, b: Bucket, planes: torch.Tensor, stride: int, alive: torch.Tensor, mode: int, tie: int,
               neg: Optional[torch.Tensor], hp: HParams, own: Optional[torch.Tensor] = None,
-              agree: Optional[torch.Tensor] = None) -> None:
+              agree: Optional[torch.Tensor] = None, rounding: int = ref.ROUND_NEAREST, seed: int = 0,
+              step: int = 0) -> None:
         self.ops.lion_vote_apply(meta, self.plan.seg_off, self._chunk_off(b), b.n_chunks, hip.DTYPE_CODE[b.dtype],
-                                 planes, stride, alive, mode, tie, neg, hp.decay, -hp.lr, own, agree)
+                                 planes, stride, alive, mode, tie, neg, hp.decay, -hp.lr, own, agree,
+                                 *_rounding_args(b, rounding, seed, step))
 
     def vote_reduce(self, recv: torch.Tensor, nbytes: int, alive: torch.Tensor, tie: int, out: torch.Tensor,
                     neg_out: Optional[torch.Tensor], ties: Optional[torch.Tensor] = None) -> None:
@@ -84,10 +107,13 @@ class TorchExecutor:
     def __init__(self, plan: FlatPlan):
         self.plan = plan
 
-    def local(self, meta, b: Bucket, hp: HParams, grads=None, moms=None, gscale=None) -> None:
+    def local(self, meta, b: Bucket, hp: HParams, grads=None, moms=None, gscale=None,
+              rounding: int = ref.ROUND_NEAREST, seed: int = 0, step: int = 0) -> None:
         assert gscale is None, "the torch executor clips gradients in place (Lion.clip_grad_norm_)"
         for s in b.segments:
-            ref.update_fn(s.param, grads[s.index], moms[s.index], hp.lr, hp.wd, hp.beta1, hp.beta2)
+            coords = _coords(b, s) if rounding != ref.ROUND_NEAREST else None
+            ref.update_fn(s.param, grads[s.index], moms[s.index], hp.lr, hp.wd, hp.beta1, hp.beta2,
+                          rounding=rounding, coords=coords, seed=seed, step=step)
 
     def encode(self, meta, b: Bucket, bits: torch.Tensor, hp: HParams, update_m: bool = True,
                stochastic: bool = False, rr: float = 0.0, seed: int = 0, step: int = 0,
@@ -113,7 +139,8 @@ class TorchExecutor:
 
     def apply(self, meta, b: Bucket, planes: torch.Tensor, stride: int, alive: torch.Tensor, mode: int, tie: int,
               neg: Optional[torch.Tensor], hp: HParams, own: Optional[torch.Tensor] = None,
-              agree: Optional[torch.Tensor] = None) -> None:
+              agree: Optional[torch.Tensor] = None, rounding: int = ref.ROUND_NEAREST, seed: int = 0,
+              step: int = 0) -> None:
         if mode == ref.VOTE_COUNTED:
             # [W][P][shard] (stride = shard bytes) -> P count planes in bucket byte order
             w = alive.numel()
@@ -141,7 +168,9 @@ class TorchExecutor:
                     live = alive.to(torch.bool)
                     twice = 2 * bits[live].to(torch.int64).sum(0)
                     agree[1] += ((twice == int(live.sum())) & (int(live.sum()) > 0)).sum().to(agree.dtype)
-            ref.apply_delta_(s.param, delta.to(s.param.device), hp.lr, hp.wd)
+            coords = _coords(b, s) if rounding != ref.ROUND_NEAREST else None
+            ref.apply_delta_(s.param, delta.to(s.param.device), hp.lr, hp.wd, rounding=rounding, coords=coords,
+                             seed=seed, step=step)
 
     def vote_reduce(self, recv: torch.Tensor, nbytes: int, alive: torch.Tensor, tie: int, out: torch.Tensor,
                     neg_out: Optional[torch.Tensor], ties: Optional[torch.Tensor] = None) -> None:

@@ -20,6 +20,17 @@ Keyword-only extensions (all optional):
                with exchange="a2a" it travels as count bit planes at
                5 <= W <= 15 and over the all-gather otherwise)
   tie_break    "negative" (reference parity) | "zero" | "positive"
+  param_rounding  "nearest" (reference parity) | "stochastic": how the update
+               kernels store bf16 parameters.  Nearest drops an update below
+               half a bf16 ulp (at lr 1e-4 every weight with |p| >= 2^-5 is
+               frozen and the weight decay never acts); stochastic rounds
+               fma(-lr, delta, p * (1 - lr*wd)) once, to one of its two bf16
+               neighbours with probability proportional to the remainder, so
+               the fp32 update survives in expectation.  The random bits are
+               a hash of (seed, step count, global coordinate) without a rank
+               term: replicas round identically.  The step count restarts on
+               resume (like the stochastic encode's stream).  fp32 parameters
+               are unaffected; fp16 parameters raise ValueError.
   exchange     vote exchange strategy, see parallel/exchange.py
   bucket_mb    packed-bit bucket size (MB) -- one collective per bucket.  None
                (default): at W > 1 the sign planes are cut into >= 4 buckets
@@ -72,6 +83,7 @@ class Lion(Optimizer):
         *,
         vote: str = "majority",
         tie_break: str = "negative",
+        param_rounding: str = "nearest",
         exchange: str = "a2a",
         bucket_mb: Optional[float] = None,
         group=None,
@@ -91,12 +103,15 @@ class Lion(Optimizer):
             raise ValueError(f"vote must be one of {tuple(ref.VOTE_CODES)}")
         if tie_break not in ref.TIE_CODES:
             raise ValueError(f"tie_break must be one of {tuple(ref.TIE_CODES)}")
+        if param_rounding not in ref.ROUNDING_CODES:
+            raise ValueError(f"param_rounding must be one of {tuple(ref.ROUNDING_CODES)}")
         defaults = dict(lr=lr, betas=betas, weight_decay=weight_decay)
         super().__init__(params, defaults)
         # stored (reference D2: it never was) but, like the reference, not part of state_dict
         self.max_grad_norm = max_grad_norm
         self.vote = vote
         self.tie_break = tie_break
+        self.param_rounding = param_rounding
         self.exchange_name = canonical_strategy(exchange)
         self.bucket_bytes = None if bucket_mb is None else int(bucket_mb * (1 << 20))
         self.process_group = group
@@ -207,6 +222,9 @@ class Lion(Optimizer):
                 backend = dist.get_backend(self.process_group)
             except (RuntimeError, ValueError):  # a simulated group has no c10d backend name
                 backend = None
+        if self.param_rounding == "stochastic" and any(p.dtype == torch.float16 for p, _ in entries):
+            raise ValueError("param_rounding='stochastic' supports bfloat16 parameters (float32 ones are stored "
+                             "exactly either way), not float16")
         plan = FlatPlan(entries, world=world, bucket_bytes=self._bucket_bytes(entries, world, backend))
         plan._full_key = key
         self._plan = plan
@@ -345,7 +363,7 @@ class Lion(Optimizer):
         if world == 1 and not self._force_vote:
             with phase_of(self.phase_timer, "local_update"):
                 for b in plan.buckets:
-                    ex.local(meta, b, hps[b.group], grads=grads, moms=moms, gscale=gscale)
+                    ex.local(meta, b, hps[b.group], grads=grads, moms=moms, gscale=gscale, **self._rounding_kw())
         else:
             self._distributed_step(plan, ex, meta, hps, grads, moms, world, rank, gscale)
         # the kernels wrote the weights through raw pointers (no autograd
@@ -370,7 +388,13 @@ class Lion(Optimizer):
             with phase_of(t, "apply"):
                 ex.apply(meta, b, a.planes, a.stride, alive, a.mode, ref.TIE_CODES[self.tie_break], a.neg,
                          hps[b.group], own=xch.send_view(b) if self.telemetry else None,
-                         agree=self._agree if self.telemetry else None)
+                         agree=self._agree if self.telemetry else None, **self._rounding_kw())
+
+    def _rounding_kw(self) -> dict:
+        """The parameter-store rounding of this step: keyed on (seed, step
+        count) only, so every rank -- and a re-vote of the same step -- rounds
+        the same way."""
+        return dict(rounding=ref.ROUNDING_CODES[self.param_rounding], seed=self.seed, step=self._n_steps)
 
     def _telemetry_setup(self, plan, xch) -> None:
         """telemetry: [agreements, ties] counters on the device, and the number
@@ -459,7 +483,7 @@ class Lion(Optimizer):
                 with phase_of(t, "apply"):
                     ex.apply(meta, b, a.planes, a.stride, alive, a.mode, tie, a.neg, hps[b.group],
                              own=xch.send_view(b) if self.telemetry else None,
-                             agree=self._agree if self.telemetry else None)
+                             agree=self._agree if self.telemetry else None, **self._rounding_kw())
             inject_fault("after_vote", self._n_steps)
             return
         # ---- somebody failed: regroup, then vote again among the survivors
@@ -487,7 +511,7 @@ class Lion(Optimizer):
             else:
                 a = rex.finish(b, None, alive2)
                 planes, stride, mode = a.planes, a.stride, a.mode
-            ex.apply(meta, b, planes, stride, alive2, mode, tie, None, hps[b.group])
+            ex.apply(meta, b, planes, stride, alive2, mode, tie, None, hps[b.group], **self._rounding_kw())
         if rex is not None:
             self._wire_carry.add(rex.wire.sent, rex.wire.recv, rex.wire.calls)
 
@@ -495,7 +519,8 @@ class Lion(Optimizer):
     def stats(self, reset: bool = True) -> dict:
         """Wire counters and (telemetry=True) vote agreement since last reset.
         Reading the agreement count synchronises with the device."""
-        out = {"world": self.last_world, "exchange": self.exchange_name, "steps": self._n_steps}
+        out = {"world": self.last_world, "exchange": self.exchange_name, "steps": self._n_steps,
+               "param_rounding": self.param_rounding}
         if self._exchange is not None or self._wire_carry.calls:
             tot = WireCounter()
             for w in (self._wire_carry, getattr(self._exchange, "wire", None)):

@@ -53,6 +53,9 @@ class LionArguments:
     lion_beta2: float = field(default=0.99, metadata={"help": "Lion beta2"})
     lion_vote: str = field(default="majority", metadata={"help": "majority | average"})
     lion_tie_break: str = field(default="negative", metadata={"help": "negative (reference) | zero | positive"})
+    lion_param_rounding: str = field(default="nearest", metadata={
+        "help": "nearest (reference) | stochastic: unbiased rounding of the bf16 parameter store, so updates "
+                "below half an ulp (lr 1e-4 at |p| >= 2^-5, any weight decay) act in expectation"})
     lion_wire: str = field(default="a2a", metadata={"help": "allgather | a2a | ref_int64"})
     lion_bucket_mb: Optional[float] = field(default=None, metadata={
         "help": "packed-bit bucket size (MB); default: automatic (>= 4 pipelined buckets at W > 1)"})
@@ -130,6 +133,7 @@ def build_lion(model: torch.nn.Module, args, lr: Optional[float] = None, weight_
         max_grad_norm=getattr(args, "lion_stochastic_max_norm", None),
         vote=getattr(args, "lion_vote", "majority"),
         tie_break=getattr(args, "lion_tie_break", "negative"),
+        param_rounding=getattr(args, "lion_param_rounding", "nearest"),
         exchange=getattr(args, "lion_wire", "a2a"),
         bucket_mb=getattr(args, "lion_bucket_mb", None),
         backend=getattr(args, "lion_backend", "auto"),

@@ -64,6 +64,8 @@ def parse():
     ap.add_argument("--exchange", default="a2a")
     ap.add_argument("--lr", type=float, default=1e-5)
     ap.add_argument("--weight_decay", type=float, default=0.0)
+    ap.add_argument("--lion_param_rounding", default="nearest", choices=["nearest", "stochastic"],
+                    help="stochastic: unbiased rounding of the bf16 parameter store (Lion(param_rounding=...))")
     ap.add_argument("--gradient_checkpointing", action="store_true")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo on cuda: rehearse N ranks on fewer GPUs (ranks share cuda:local%%ngpu)")
@@ -106,7 +108,7 @@ def main():
     broadcast_parameters(model)
     el = ElasticGroup.get(a.elastic_timeout, grace_s=a.elastic_grace)
     opt = Lion([p for p in model.parameters() if p.requires_grad], lr=a.lr, weight_decay=a.weight_decay,
-               exchange=a.exchange, elastic_timeout=a.elastic_timeout)
+               exchange=a.exchange, elastic_timeout=a.elastic_timeout, param_rounding=a.lion_param_rounding)
     step_fn = TrainStep(model, opt, grad_accum=a.grad_accum, max_grad_norm=1.0)
     gen = torch.Generator(device=dev).manual_seed(1000 + rank)
 

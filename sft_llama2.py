@@ -22,7 +22,7 @@
   present in the HF cache; a name that resolves to nothing is an error, and
   ``--synthetic_data`` trains on a synthetic corpus of the same format;
 * every Lion knob of run_clm (``--lion_beta1/2``, ``--lion_vote``,
-  ``--lion_tie_break``, ``--lion_wire``, ``--lion_bucket_mb``,
+  ``--lion_tie_break``, ``--lion_param_rounding``, ``--lion_wire``, ``--lion_bucket_mb``,
   ``--lion_stochastic_max_norm``, ``--lion_dropout_schedule`` and
   ``--lion_elastic_timeout`` for real worker dropout);
 * saves the adapter (final_checkpoint/) and the merged model

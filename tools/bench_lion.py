@@ -3,10 +3,17 @@ K0 local update, K1 encode (momentum + 1-bit pack), K2 vote+apply over W
 fake voter planes, K4 shard vote (a2a), the average vote's byte kernel against
 its a2a path (K4c shard count + counted apply), over the GPT-2 small and the
 Llama-3-8B parameter sets (shapes only, random values).  Bytes per param are
-the kernels' compulsory traffic; prints us, GB/s and % of 6.3 TB/s.
+the kernels' compulsory traffic; prints us (median, min-max over the rounds),
+GB/s and % of 6.3 TB/s.
 
-  python tools/bench_lion.py [gpt2|llama3] [W]
+  python tools/bench_lion.py [gpt2|llama3] [W] [--param_rounding nearest|stochastic|both]
+
+``--param_rounding both`` times K0 and the pre-voted K2 with the nearest and
+the stochastic parameter store interleaved in one process (the cost of the
+coordinate hash); ``--only_rounding`` keeps just those cases.  With
+``DLION_LIB`` naming an earlier build of the extension, use ``nearest``.
 """
+import argparse
 import statistics
 import sys
 
@@ -44,8 +51,16 @@ def timed(fn, reps=5):
 
 
 def main():
-    model = sys.argv[1] if len(sys.argv) > 1 else "gpt2"
-    W = int(sys.argv[2]) if len(sys.argv) > 2 else 8
+    ap = argparse.ArgumentParser()
+    ap.add_argument("model", nargs="?", default="gpt2", choices=["gpt2", "llama3"])
+    ap.add_argument("W", nargs="?", type=int, default=8)
+    ap.add_argument("--param_rounding", default="nearest", choices=["nearest", "stochastic", "both"])
+    ap.add_argument("--only_rounding", action="store_true", help="only K0, the pre-voted K2 and the copy")
+    ap.add_argument("--rounds", type=int, default=3)
+    a = ap.parse_args()
+    model, W = a.model, a.W
+    sr = dict(rounding=ref.ROUND_STOCHASTIC, seed=1, step=1)
+    base_kw = sr if a.param_rounding == "stochastic" else {}
     dev = torch.device("cuda")
     ps = [torch.randn(s, device=dev, dtype=torch.bfloat16) for s in shapes(model)]
     gs = [torch.randn_like(p) for p in ps]
@@ -62,7 +77,11 @@ def main():
 
     def local():
         for b in plan.buckets:
-            hx.local(meta, b, hp)
+            hx.local(meta, b, hp, **base_kw)
+
+    def local_sr():
+        for b in plan.buckets:
+            hx.local(meta, b, hp, **sr)
 
     def encode():
         for b in plan.buckets:
@@ -71,12 +90,17 @@ def main():
     def apply():
         for b in plan.buckets:
             pl = planes[W * b.byte_off: W * (b.byte_off + b.nbytes)]
-            hx.apply(meta, b, pl, b.nbytes, alive, ref.VOTE_MAJORITY, ref.TIE_NEGATIVE, None, hp)
+            hx.apply(meta, b, pl, b.nbytes, alive, ref.VOTE_MAJORITY, ref.TIE_NEGATIVE, None, hp, **base_kw)
 
     def apply_prevoted():  # a2a (default exchange): one voted plane after the shard vote + all-gather
         for b in plan.buckets:
             hx.apply(meta, b, planes[b.byte_off: b.byte_off + b.nbytes], b.nbytes, alive, ref.VOTE_PREVOTED,
-                     ref.TIE_NEGATIVE, None, hp)
+                     ref.TIE_NEGATIVE, None, hp, **base_kw)
+
+    def apply_prevoted_sr():
+        for b in plan.buckets:
+            hx.apply(meta, b, planes[b.byte_off: b.byte_off + b.nbytes], b.nbytes, alive, ref.VOTE_PREVOTED,
+                     ref.TIE_NEGATIVE, None, hp, **sr)
 
     def vote_reduce():  # a2a: this rank's shard of every bucket, W planes of it
         for b in plan.buckets:
@@ -87,7 +111,7 @@ def main():
     # average vote: the byte kernel over the W gathered planes (all-gather exchange) against the
     # a2a path's K4c shard count + counted apply from the [W][P][shard] count planes (W <= 15)
     P = W.bit_length()
-    counted = W <= 15
+    counted = W <= 15 and not a.only_rounding
     if counted:
         shard_counts = torch.zeros(P * plan.total_bytes // W, dtype=torch.uint8, device=dev)
         counts = torch.zeros(P * plan.total_bytes, dtype=torch.uint8, device=dev)
@@ -101,12 +125,12 @@ def main():
     def apply_average():
         for b in plan.buckets:
             pl = planes[W * b.byte_off: W * (b.byte_off + b.nbytes)]
-            hx.apply(meta, b, pl, b.nbytes, alive, ref.VOTE_AVERAGE, ref.TIE_NEGATIVE, None, hp)
+            hx.apply(meta, b, pl, b.nbytes, alive, ref.VOTE_AVERAGE, ref.TIE_NEGATIVE, None, hp, **base_kw)
 
     def apply_counted():
         for b in plan.buckets:
             hx.apply(meta, b, counts[P * b.byte_off: P * (b.byte_off + b.nbytes)], b.nbytes // W, alive,
-                     ref.VOTE_COUNTED, ref.TIE_NEGATIVE, None, hp)
+                     ref.VOTE_COUNTED, ref.TIE_NEGATIVE, None, hp, **base_kw)
 
     def vote_count():  # a2a + average: this rank's shard of every bucket, W planes in, P count planes out
         for b in plan.buckets:
@@ -126,18 +150,27 @@ def main():
              f"K2 vote+apply W={W}": (apply, 4.0 + W / 8), "K2 prevoted apply": (apply_prevoted, 4.0 + 1 / 8), f"K4 shard vote W={W}": (vote_reduce, (W + 1) / 8 / W),
              "bf16 copy (reference)": (copy, 4.0)}
     cases[f"K2 average (byte kernel) W={W}"] = (apply_average, 4.0 + W / 8)
+    if a.only_rounding:
+        cases = {k: v for k, v in cases.items() if k in ("K0 local", "K2 prevoted apply", "bf16 copy (reference)")}
+    if a.param_rounding == "both":  # beside their nearest twins: the rounds interleave them
+        twins = {"K0 local": ("K0 local (stochastic)", local_sr),
+                 "K2 prevoted apply": ("K2 prevoted apply (stochastic)", apply_prevoted_sr)}
+        cases = {kk: vv for k, v in cases.items()
+                 for kk, vv in ([(k, v)] + ([(twins[k][0], (twins[k][1], v[1]))] if k in twins else []))}
     if counted:
         cases[f"K2 counted apply W={W}"] = (apply_counted, 4.0 + P / 8)
         cases[f"K4c shard count W={W}"] = (vote_count, (W + P) / 8 / W)
-    print(f"{model}: {n / 1e6:.1f}M params, {len(ps)} tensors, {len(plan.buckets)} buckets", flush=True)
+    print(f"{model}: {n / 1e6:.1f}M params, {len(ps)} tensors, {len(plan.buckets)} buckets, "
+          f"param_rounding={a.param_rounding}, lib={hip.LIB_PATH.name}", flush=True)
     res = {k: [] for k in cases}
-    for _ in range(3):
+    for _ in range(a.rounds):
         for k, (f, _) in cases.items():
             res[k].append(timed(f))
     for k, (f, bpp) in cases.items():
         us = statistics.median(res[k])
         gbs = bpp * n / us / 1e3
-        print(f"  {k:30s} {us:9.1f} us  {gbs:7.0f} GB/s  {100 * gbs * 1e9 / HBM:5.1f}% of 6.3 TB/s", flush=True)
+        print(f"  {k:32s} {us:9.1f} us ({min(res[k]):.1f}-{max(res[k]):.1f})  {gbs:7.0f} GB/s  "
+              f"{100 * gbs * 1e9 / HBM:5.1f}% of 6.3 TB/s", flush=True)
 
 
 if __name__ == "__main__":
