@@ -144,8 +144,20 @@ __global__ void __launch_bounds__(1024) colsum_kernel(const uint16_t* __restrict
 // Llama MLP activation h = silu(g) * u (HF LlamaMLP: act_fn(gate_proj(x)) *
 // up_proj(x)), one pass each way: ATen needs silu + mul forward and
 // mul / silu_backward / mul backward with fp32 -> bf16 round trips between.
-__device__ __forceinline__ float sigmoid_f(float a) {
-  return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-a * 1.4426950408889634f));
+// sigmoid(a) = s * k with k = 1 down to a = -80.  Below that, both terms of 1 + 2^t
+// (t = -a log2 e) are scaled by k = 2^-64 before the reciprocal and the callers multiply
+// by k last: sigmoid(a) drops below 2^-126 at a = -87.4 and exp2 overflows at t = 128
+// (a = -88.7, rcp(inf) = 0), but a sigmoid(a) is still 2e-37 there and must not come out
+// as 0.  s stays a normal number down to a = -131.  With k = 1 every product is bit for
+// bit what rcp(1 + exp2(t)) gives; t - 64 is exact (t > 115).
+struct Sigmoid {
+  float s, k;
+};
+__device__ __forceinline__ Sigmoid sigmoid_scaled(float a) {
+  const float t = -a * 1.4426950408889634f;
+  const bool far = a < -80.f;
+  const float k = far ? 0x1p-64f : 1.f;
+  return {__builtin_amdgcn_rcpf(k + __builtin_amdgcn_exp2f(far ? t - 64.f : t)), k};
 }
 
 // Row geometry: rows x F, inputs g / u at row stride ld_in (the two halves of a
@@ -162,7 +174,10 @@ __global__ void __launch_bounds__(256) swiglu_fwd_kernel(const uint16_t* __restr
     Elem<kBF16>::load8(g + src, gv);
     Elem<kBF16>::load8(u + src, uv);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = gv[j] * sigmoid_f(gv[j]) * uv[j];
+    for (int j = 0; j < 8; ++j) {
+      const Sigmoid sc = sigmoid_scaled(gv[j]);
+      o[j] = gv[j] * sc.s * uv[j] * sc.k;
+    }
     Elem<kBF16>::store8(h + i * 8, o);
   }
 }
@@ -182,9 +197,10 @@ __global__ void __launch_bounds__(256) swiglu_bwd_kernel(const uint16_t* __restr
     Elem<kBF16>::load8(u + src, uv);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const float sg = sigmoid_f(gv[j]);
-      ou[j] = dv[j] * gv[j] * sg;
-      og[j] = dv[j] * uv[j] * sg * (1.f + gv[j] * (1.f - sg));
+      const Sigmoid sc = sigmoid_scaled(gv[j]);
+      const float sg = sc.s * sc.k;  // may flush to 0: only 1 - sg takes it
+      ou[j] = dv[j] * gv[j] * sc.s * sc.k;
+      og[j] = dv[j] * uv[j] * sc.s * (1.f + gv[j] * (1.f - sg)) * sc.k;
     }
     Elem<kBF16>::store8(dg + dst, og);
     Elem<kBF16>::store8(du + dst, ou);
@@ -209,7 +225,8 @@ __global__ void __launch_bounds__(256) swiglu_fwd_t_kernel(const uint16_t* __res
     Elem<kBF16>::load8(u + row * ld_in + c, uv);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      o[j] = gv[j] * sigmoid_f(gv[j]) * uv[j];
+      const Sigmoid sc = sigmoid_scaled(gv[j]);
+      o[j] = gv[j] * sc.s * uv[j] * sc.k;
       th[tr][tc + j] = f32_to_bf16(o[j]);
     }
     Elem<kBF16>::store8(h + row * F + c, o);
@@ -249,9 +266,10 @@ __global__ void __launch_bounds__(256) swiglu_bwd_t_kernel(const uint16_t* __res
     Elem<kBF16>::load8(u + row * ld_in + c, uv);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const float sg = sigmoid_f(gv[j]);
-      ou[j] = dv[j] * gv[j] * sg;
-      og[j] = dv[j] * uv[j] * sg * (1.f + gv[j] * (1.f - sg));
+      const Sigmoid sc = sigmoid_scaled(gv[j]);
+      const float sg = sc.s * sc.k;  // may flush to 0: only 1 - sg takes it
+      ou[j] = dv[j] * gv[j] * sc.s * sc.k;
+      og[j] = dv[j] * uv[j] * sc.s * (1.f + gv[j] * (1.f - sg)) * sc.k;
       tg[tr][tc + j] = f32_to_bf16(og[j]);
       tu[tr][tc + j] = f32_to_bf16(ou[j]);
     }

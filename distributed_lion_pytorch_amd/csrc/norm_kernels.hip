@@ -174,7 +174,14 @@ add_norm_fwd_body(const uint16_t* __restrict__ x, const uint16_t* __restrict__ y
     for (int j = 0; j < 4; ++j) s += v[k][j];  // a masked chunk adds zeros
   }
   float mean = 0.f;
-  if constexpr (!RMS) mean = gsum2<WPR>(s, 0.f, scratch).x * inv_c;
+  if constexpr (!RMS) {
+    // the product is rounded once, here: left contractable, hipcc fused it into every
+    // (v - mean) below as fma(-sum, inv_c, v), so that h and rstd were taken about a mean
+    // that differs from the one stored for the backward by up to 2^-24 |mean| (a row
+    // element equal to the stored mean did not normalise to beta)
+#pragma clang fp contract(off)
+    mean = gsum2<WPR>(s, 0.f, scratch).x * inv_c;
+  }
   float q = 0.f;
 #pragma unroll
   for (int k = 0; k < NS; ++k) {

@@ -536,3 +536,22 @@ def assert_within(got, ref64, bound, name=""):
         raise AssertionError(f"{name}: {int((ratio > 1).sum())} of {ratio.numel()} elements over the bound; first at {i}: "
                              f"got {float(g[i]):.6e}  ref {float(r[i]):.6e}  bound {float(b[i]):.3e}")
     return worst
+
+
+# ---------------------------------------------------------------------------
+# Norm, SwiGLU, RoPE and partial sums (tests/test_norm_exact_*.py,
+# tests/test_elementwise_exact_*.py, docs/TEST_TOLERANCES.md).
+
+# the smallest normal fp32 (and bf16) number: below it the kernels' exp2 / rcp flush to zero
+MIN_NORMAL = 2.0 ** -126
+
+
+def assert_rounded_uflow(got, ref64, floor, name=""):
+    """assert_rounded, except that an element whose reference is below 2^-126 (the smallest normal fp32 and bf16
+    number) may be zero or the reference: it is judged against 0 when it is 0, and otherwise with half the spacing
+    of the bf16 subnormals (2^-134) added to its bound."""
+    tiny = ref64.abs() < MIN_NORMAL
+    zero = tiny & (got.double() == 0)
+    ref = torch.where(zero, torch.zeros_like(ref64), ref64)
+    fl = floor + torch.where(tiny & ~zero, torch.full_like(ref64, 2.0 ** -134), torch.zeros_like(ref64))
+    return assert_rounded(got, ref, fl, name)
