@@ -69,17 +69,19 @@ void lion_local(const Tensor& meta, int64_t seg_off, int64_t chunk_off, int64_t 
 
 void lion_encode(const Tensor& meta, int64_t seg_off, int64_t chunk_off, int64_t n_chunks, int64_t dtype,
                  const Tensor& bits, double b1, double omb1, double b2, double omb2, bool update_m,
-                 bool stochastic, double rr, int64_t seed, int64_t step, const std::optional<Tensor>& gscale) {
+                 bool stochastic, double rr, int64_t seed, int64_t step, const std::optional<Tensor>& gscale,
+                 int64_t cbase) {
   check_dev(meta, "meta");
   check_dev(bits, "bits");
   TORCH_CHECK(bits.scalar_type() == at::kByte, "dlion: bits must be uint8");
+  TORCH_CHECK(cbase >= 0 && cbase % 8 == 0, "dlion: the coordinate base must be a multiple of 8");
   const c10::DeviceGuard g(meta.device());
   const int64_t* base = meta.data_ptr<int64_t>();
   check_hip(dlion::launch_lion_encode(static_cast<int>(dtype), base + seg_off, base + chunk_off, n_chunks,
                                       bits.data_ptr<uint8_t>(), static_cast<float>(b1), static_cast<float>(omb1),
                                       static_cast<float>(b2), static_cast<float>(omb2), update_m ? 1 : 0,
                                       stochastic ? 1 : 0, static_cast<float>(rr), static_cast<uint64_t>(seed),
-                                      static_cast<uint32_t>(step), gscale_ptr(gscale), cur_stream()),
+                                      static_cast<uint32_t>(step), gscale_ptr(gscale), cur_stream(), cbase),
             "lion_encode");
 }
 
@@ -1252,7 +1254,7 @@ TORCH_LIBRARY(dlion, m) {
   m.def(
       "lion_encode(Tensor meta, int seg_off, int chunk_off, int n_chunks, int dtype, Tensor(a!) bits, float b1,"
       " float omb1, float b2, float omb2, bool update_m, bool stochastic, float rr, int seed, int step,"
-      " Tensor? gscale=None) -> ()");
+      " Tensor? gscale=None, int cbase=0) -> ()");
   m.def("grad_sumsq(Tensor meta, int seg_off, int chunk_off, int n_chunks, int dtype, Tensor(a!) partial,"
         " int part_off) -> ()");
   m.def("clip_coef(Tensor partial, int n, float max_norm, Tensor(a!) out) -> ()");

@@ -15,7 +15,8 @@ hipError_t launch_lion_local(int dt, const int64_t* seg, const int64_t* chunks, 
                              hipStream_t st, int rounding = 0, uint32_t rkey = 0, int64_t cbase = 0);
 hipError_t launch_lion_encode(int dt, const int64_t* seg, const int64_t* chunks, int64_t n_chunks, uint8_t* bits,
                               float b1, float omb1, float b2, float omb2, int update_m, int stochastic, float rr,
-                              uint64_t seed, uint32_t step, const float* gscale, hipStream_t st);
+                              uint64_t seed, uint32_t step, const float* gscale, hipStream_t st,
+                              int64_t cbase = 0);  // stochastic: global coordinate of the bucket's first bit
 // fused clip_grad_norm_: per-chunk sum of squares, then norm + clip coefficient on device
 hipError_t launch_grad_sumsq(int dt, const int64_t* seg, const int64_t* chunks, int64_t n_chunks, float* partial,
                              hipStream_t st);

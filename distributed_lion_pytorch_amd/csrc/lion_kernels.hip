@@ -221,12 +221,17 @@ __device__ __forceinline__ void store_quad_bits(uint8_t* bits, int64_t bit, uint
 // bits: this rank's packed sign plane for the bucket (bucket-relative bit_off).
 // stochastic: bit = Bernoulli(clamp((u + rr) / (2 rr), 0, 1)) with
 //   rr = (1 + 1/b1) * max_grad_norm  (ref :106-108, clamped: SURVEY D4).
+//   The uniform of global coordinate c = cbase + bit_off + e (cbase = 8 * the
+//   bucket's byte offset, as for the stochastic parameter store) is word c & 3
+//   of Philox4x32-10 under the key (seed_lo, seed_hi) at the counter
+//   (lo32(c & ~7), hi32(c & ~7), step, (c & 7) >> 2): a lane's 8 coordinates
+//   take two calls.  The oracle is ops/reference.py::stochastic_bits_exact.
 template <int DT, bool STOC>
 __global__ void __launch_bounds__(kThreads)
 lion_encode_kernel(const int64_t* __restrict__ seg, const int64_t* __restrict__ chunks,
                    uint8_t* __restrict__ bits, float b1, float omb1, float b2, float omb2,
                    int update_m, float rr, uint32_t seed_lo, uint32_t seed_hi, uint32_t step,
-                   const float* __restrict__ gscale) {
+                   const float* __restrict__ gscale, int64_t cbase) {
   using E = Elem<DT>;
   using S = typename E::S;
   const int64_t s = chunks[2 * blockIdx.x], start = chunks[2 * blockIdx.x + 1];
@@ -277,7 +282,9 @@ lion_encode_kernel(const int64_t* __restrict__ seg, const int64_t* __restrict__ 
 #pragma unroll
       for (int j = 0; j < 8; ++j) u[j] = E::rnd(__fmaf_rn(gv[j], omb1, E::rnd(mv[j] * b1)));
       if constexpr (STOC) {
-        const uint64_t gi = static_cast<uint64_t>(r.bit_off + e);  // unique per element
+        // the lane's first global coordinate (a multiple of 8), as in sr_round8:
+        // unique per lane across the plan, so no two buckets share a draw
+        const uint64_t gi = static_cast<uint64_t>(cbase + r.bit_off + e);
         const uint4 c0 = philox4x32_10(
             make_uint4(static_cast<uint32_t>(gi), static_cast<uint32_t>(gi >> 32), step, 0u),
             make_uint2(seed_lo, seed_hi));
@@ -1170,15 +1177,15 @@ hipError_t launch_lion_local(int dt, const int64_t* seg, const int64_t* chunks, 
 hipError_t launch_lion_encode(int dt, const int64_t* seg, const int64_t* chunks, int64_t n_chunks,
                               uint8_t* bits, float b1, float omb1, float b2, float omb2, int update_m,
                               int stochastic, float rr, uint64_t seed, uint32_t step, const float* gscale,
-                              hipStream_t st) {
+                              hipStream_t st, int64_t cbase) {
   if (n_chunks == 0) return hipSuccess;
   const uint32_t lo = static_cast<uint32_t>(seed), hi = static_cast<uint32_t>(seed >> 32);
   if (stochastic) {
     DLION_DISPATCH(dt, hipLaunchKernelGGL((lion_encode_kernel<DT, true>), dim3(n_chunks), dim3(kThreads), 0,
-                                          st, seg, chunks, bits, b1, omb1, b2, omb2, update_m, rr, lo, hi, step, gscale));
+                                          st, seg, chunks, bits, b1, omb1, b2, omb2, update_m, rr, lo, hi, step, gscale, cbase));
   } else {
     DLION_DISPATCH(dt, hipLaunchKernelGGL((lion_encode_kernel<DT, false>), dim3(n_chunks), dim3(kThreads), 0,
-                                          st, seg, chunks, bits, b1, omb1, b2, omb2, update_m, rr, lo, hi, step, gscale));
+                                          st, seg, chunks, bits, b1, omb1, b2, omb2, update_m, rr, lo, hi, step, gscale, cbase));
   }
   return hipGetLastError();
 }

@@ -317,6 +317,82 @@ def apply_delta_(p: torch.Tensor, delta: torch.Tensor, lr: float, wd: float, rou
     p.add_(delta.view(p.shape), alpha=-lr)
 
 
+# ------------------------------------------- stochastic binarisation, exact
+# The oracle of K3 (csrc/lion_kernels.hip: lion_encode_kernel<DT, true>): the
+# kernel's Philox4x32-10 draw and its fp32 probability, reproduced with int64
+# tensors masked to 32 bits and correctly rounded fp32 ops -- no
+# torch.Generator, so the bits are a pure function of (seed, step, global
+# coordinate) and the same on every backend.
+_PHILOX_M0, _PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
+_PHILOX_W0, _PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+
+
+def _mulhilo32(a: int, x):
+    """(hi32, lo32) of the 64-bit product of the constant ``a`` and the 32-bit
+    values ``x`` (a Python int or an int64 tensor), in 16-bit limbs of ``x`` so
+    that no intermediate leaves 63 bits."""
+    ph, pl = a * (x >> 16), a * (x & 0xFFFF)  # each below 2^48
+    return (ph + (pl >> 16)) >> 16, (((ph & 0xFFFF) << 16) + pl) & _M32
+
+
+def philox4x32_10(ctr4, key2):
+    """Philox4x32-10 (the recurrence of csrc/common.h) on 32-bit values held
+    in Python ints or int64 tensors: counter ``(x, y, z, w)`` and key
+    ``(k0, k1)`` -> the four output words."""
+    x, y, z, w = ctr4
+    k0, k1 = key2
+    for _ in range(10):
+        hi0, lo0 = _mulhilo32(_PHILOX_M0, x)
+        hi1, lo1 = _mulhilo32(_PHILOX_M1, z)
+        x, y, z, w = hi1 ^ y ^ k0, lo1, hi0 ^ w ^ k1, lo0
+        k0, k1 = (k0 + _PHILOX_W0) & _M32, (k1 + _PHILOX_W1) & _M32
+    return x, y, z, w
+
+
+def stoc_unit(coords: torch.Tensor, seed: int, step: int) -> torch.Tensor:
+    """fp32 uniforms in [0, 1) of the global coordinates ``coords`` (int64).
+
+    Coordinate c takes word ``c & 3`` of the counter ``(lo32(c8), hi32(c8),
+    step & 0xFFFFFFFF, (c & 7) >> 2)`` with ``c8 = c & ~7`` under the key
+    ``(lo32(seed), hi32(seed))``, as ``float(word >> 8) * 2^-24``: the
+    kernel's lane layout (8 coordinates per lane from two Philox calls).  A
+    lane starts at a multiple of 8 because every tensor's bits start at a
+    multiple of 2048 above a coordinate base that is a multiple of 8."""
+    c = coords.to(torch.int64).reshape(-1)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    c8 = c & ~7
+    words = philox4x32_10((c8 & _M32, (c8 >> 32) & _M32, torch.full_like(c, int(step) & _M32), (c & 7) >> 2),
+                          (seed & _M32, seed >> 32))
+    word = torch.stack(words).gather(0, (c & 3).unsqueeze(0)).squeeze(0)
+    return (word >> 8).to(torch.float32) * 2.0 ** -24
+
+
+def interp_exact(grad: torch.Tensor, exp_avg: torch.Tensor, beta1: float) -> torch.Tensor:
+    """The kernels' expression of :func:`interp`, in the tensors' dtype:
+    ``rnd(fma32(g, fp32(1 - beta1), rnd(fp32(m) * fp32(beta1))))`` with ``rnd``
+    the rounding to the dtype (the identity for fp32)."""
+    dt = grad.dtype
+    b1 = torch.tensor(beta1, dtype=torch.float32, device=grad.device)
+    mb = (exp_avg.float() * b1).to(dt).float()
+    return _fma32(1 - beta1, grad.float(), mb).to(dt)
+
+
+def stochastic_bits_exact(grad, exp_avg, beta1: float, rr: float, coords: torch.Tensor, seed: int,
+                          step: int) -> torch.Tensor:
+    """K3's vote bits, exactly: ``stoc_unit(coords) < clamp((u + rr) * (0.5 /
+    rr), 0, 1)`` with ``u = interp_exact(g, m, beta1)`` and every op in fp32
+    (``rr`` rounded to fp32 first; an add then a multiply, no fma).  A NaN
+    ``u`` gives 0, +inf gives 1, -inf gives 0.  ``coords``: the elements'
+    global coordinates, the first one a multiple of 8 (a lane boundary)."""
+    c = coords.to(torch.int64).reshape(-1)
+    assert c.numel() == grad.numel() and (c.numel() == 0 or int(c[0]) % 8 == 0), "a tensor starts on a lane boundary"
+    u = interp_exact(grad, exp_avg, beta1).float().reshape(-1)
+    rr32 = torch.tensor(rr, dtype=torch.float32, device=u.device)
+    inv = torch.tensor(0.5, dtype=torch.float32, device=u.device) / rr32
+    pr = ((u + rr32) * inv).clamp(0.0, 1.0)
+    return (stoc_unit(c, seed, step).to(u.device) < pr).view(grad.shape)
+
+
 # ------------------------------------------- reference-compatible functions
 def update_fn(p, grad, exp_avg, lr, wd, beta1, beta2, rounding: int = ROUND_NEAREST,
               coords: Optional[torch.Tensor] = None, seed: int = 0, step: int = 0) -> None:

@@ -36,7 +36,8 @@ def _region_bytes(numel: int) -> int:
 def coord_base(b: Bucket) -> int:
     """Global coordinate of the bucket's first bit: element e of segment s has
     the coordinate ``coord_base(b) + s.bit_off + e``, unique across the plan
-    and the same on every rank (what the stochastic parameter rounding hashes)."""
+    and the same on every rank (what the stochastic parameter rounding hashes
+    and the stochastic encode draws at)."""
     return 8 * b.byte_off
 
 
@@ -49,6 +50,8 @@ def _rounding_args(b: Bucket, rounding: int, seed: int, step: int):
 
 
 def _coords(b: Bucket, s) -> torch.Tensor:
+    # a kernel lane's 8 coordinates share one aligned group of 8 (what sr_bits16 and stoc_unit rely on)
+    assert s.bit_off % ALIGN_ELEMS == 0 and coord_base(b) % 8 == 0
     return coord_base(b) + s.bit_off + torch.arange(s.numel, dtype=torch.int64, device=s.param.device)
 
 
@@ -73,7 +76,8 @@ class HipExecutor:
                grads=None, moms=None, gscale=None) -> None:
         self.ops.lion_encode(meta, self.plan.seg_off, self._chunk_off(b), b.n_chunks, hip.DTYPE_CODE[b.dtype], bits,
                              hp.beta1, 1.0 - hp.beta1, hp.beta2, 1.0 - hp.beta2, update_m, stochastic, rr,
-                             seed & 0x7FFFFFFFFFFFFFFF, step & 0xFFFFFFFF, gscale)
+                             seed & 0x7FFFFFFFFFFFFFFF, step & 0xFFFFFFFF, gscale,
+                             *((coord_base(b),) if stochastic else ()))
 
     def grad_sumsq(self, meta, b: Bucket, partial: torch.Tensor) -> None:
         """partial[b.chunk_off + i] = sum of g^2 over chunk i of bucket b."""
@@ -119,16 +123,11 @@ class TorchExecutor:
                stochastic: bool = False, rr: float = 0.0, seed: int = 0, step: int = 0,
                grads=None, moms=None, gscale=None) -> None:
         assert gscale is None, "the torch executor clips gradients in place (Lion.clip_grad_norm_)"
-        gen = None
-        if stochastic:
-            gen = torch.Generator(device=bits.device)
-            gen.manual_seed((seed * 1_000_003 + step) & 0x7FFFFFFFFFFFFFFF)
         for s in b.segments:
             g, m = grads[s.index], moms[s.index]
             if stochastic:
-                # rr = (1 + 1/b1) * max_grad_norm  ->  recover max_grad_norm for the oracle
-                mgn = rr / (1 + 1 / hp.beta1)
-                vb = ref.stochastic_bits(g, m, hp.beta1, mgn, gen)
+                # the kernel's draw: Philox at the global coordinate, so no two buckets repeat a stream
+                vb = ref.stochastic_bits_exact(g, m, hp.beta1, rr, _coords(b, s), seed & 0x7FFFFFFFFFFFFFFF, step)
             else:
                 vb = ref.sign_bits(g, m, hp.beta1)
             nb = _region_bytes(s.numel)
