@@ -39,6 +39,13 @@ struct AttnArgs {
   // q - window < k <= q; 0 = plain causal.  Key / query tiles wholly outside
   // the window are skipped, the boundary tiles masked per element.
   int window;
+  // nullable [B][T] int32 per-row key bounds (document-isolated packing), both
+  // or neither: query q attends keys row_lo[q] <= k <= q, and key k is seen by
+  // queries k <= q < key_hi[k] -- the same relation from either side.  The
+  // host guarantees 0 <= row_lo[q] <= q, k < key_hi[k] <= T, both
+  // non-decreasing along T, and window == 0 (folded into the bounds).
+  const int32_t* row_lo;
+  const int32_t* key_hi;
 };
 
 }  // namespace dlion

@@ -442,6 +442,20 @@ struct SlideRange {
       lim = -1;
     }
   }
+  // Per-row key bounds (document-isolated packing): `lo` = row_lo of the batch
+  // row, non-decreasing, so the tile's first row has the lowest bound.  Every
+  // tile index is clamped to the causal range [0, min(tile, ntiles - 1)] and
+  // every read of the array to row T - 1: arrays that break the preconditions
+  // give wrong numbers, never an address outside K / V.
+  __device__ __forceinline__ SlideRange(const int32_t* lo, int T, int qtile, int w, int nt) {
+    const int ntl = ntiles32(T) - 1;
+    const int l0 = lo[min(qtile * 32, T - 1)], lb = lo[min((qtile - w) * 32, T - 1)];
+    // readfirstlane: hipcc folds the clamps into v_min3 / v_med3 (VALU only);
+    // the results steer scalar branches and the DMA's SGPR tile base
+    wlo = __builtin_amdgcn_readfirstlane(min(max(l0 >> 5, 0), min(qtile, ntl)));
+    kstart = (__builtin_amdgcn_readfirstlane(min(max(lb >> 5, 0), min(qtile - w, ntl))) / nt) * nt;
+    lim = lo[min(qtile * 32 + 31, T - 1)] - 1;  // keys <= lim are below the bound of the tile's last valid row
+  }
   // a key-tile group starting at tile kt holds keys outside some row's window
   __device__ __forceinline__ bool cut(int kt, int) const { return kt * 32 <= lim; }
 };
@@ -456,6 +470,22 @@ __device__ __forceinline__ void window_mask_qlane(f32x16 (&s)[NT], int kt, int q
       if ((kt + j) * 32 + acc_row(reg, hf) <= q - window) s[j][reg] = -INFINITY;
 }
 
+// the same with a per-row bound: -inf where key < lo (the lane's row_lo)
+template <int NT>
+__device__ __forceinline__ void bound_mask_qlane(f32x16 (&s)[NT], int kt, int lo, int hf) {
+#pragma unroll
+  for (int j = 0; j < NT; ++j)
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg)
+      if ((kt + j) * 32 + acc_row(reg, hf) < lo) s[j][reg] = -INFINITY;
+}
+// the key range of a query-side wave: from the window, or (BOUNDS) from row_lo
+template <bool BOUNDS>
+__device__ __forceinline__ SlideRange key_range(const AttnArgs& a, int b, int window, int qtile, int w, int nt) {
+  if constexpr (BOUNDS) return SlideRange(a.row_lo + static_cast<int64_t>(b) * a.T, a.T, qtile, w, nt);
+  else return SlideRange(window, qtile, w, nt);
+}
+
 // ------------------------------------------------------------------ forward
 // NT key tiles (32 keys each) per barrier: with NT = 2 every wave has two
 // independent QK^T chains and two PV chains per iteration, so hipcc can put one
@@ -463,8 +493,12 @@ __device__ __forceinline__ void window_mask_qlane(f32x16 (&s)[NT], int kt, int q
 // the QK -> max -> exp -> PV chain waits for the previous one.  (Software-
 // pipelined variants -- QK^T of the next tile issued before this tile's
 // softmax -- measured neutral to -1 % in round 3 and were removed.)
-template <int D, bool DROP, int NT>
+// BOUNDS (all three kernels; D = 128 without dropout only): per-row key bounds
+// row_lo / key_hi (attention.h) take the window's place -- the same skipped
+// tiles and boundary-tile element masks, the bound read per row.
+template <int D, bool DROP, int NT, bool BOUNDS = false>
 __global__ void __launch_bounds__(256) attn_fwd_kernel(AttnArgs a) {
+  static_assert(!BOUNDS || (D == 128 && !DROP), "bounds: D = 128 without dropout");
   __shared__ __attribute__((aligned(16))) LdsTile<D> ks_[2][NT];
   __shared__ __attribute__((aligned(16))) LdsTile<D> vs_[2][NT];
   const int lane = threadIdx.x & 63, r = lane & 31, hf = lane >> 5;
@@ -475,8 +509,9 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(AttnArgs a) {
   // rows past T (tail tile): computed on a copy of row T-1, never stored; keys
   // past T are behind every valid query, so the causal mask already drops them
   const int qc = min(q, a.T - 1);
-  const int win = window_of<D>(a);
-  const SlideRange sw(win, qtile, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), NT);
+  const int win = BOUNDS ? 0 : window_of<D>(a);
+  const SlideRange sw = key_range<BOUNDS>(a, b, win, qtile, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), NT);
+  const int lo_q = BOUNDS ? a.row_lo[static_cast<int64_t>(b) * a.T + qc] : 0;
 
   bf16x8 qf[D / 16];
   if (blk.active) {
@@ -489,7 +524,7 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(AttnArgs a) {
   for (int t = 0; t < D / 32; ++t) oacc[t] = zero16();
   // a finite start under a sliding window: a row whose keys in the wave's first
   // tile are all masked then gets p = 0 there instead of exp2(-inf + inf)
-  float m = win > 0 ? -1e30f : -INFINITY, l = 0.f;
+  float m = (BOUNDS || win > 0) ? -1e30f : -INFINITY, l = 0.f;
 
   const __bf16* kg = a.k + b * a.k_sb + hk * a.k_sh;
   const __bf16* vg = a.v + b * a.v_sb + hk * a.v_sh;
@@ -543,7 +578,10 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(AttnArgs a) {
           for (int reg = 0; reg < 16; ++reg)
             if ((kt + j) * 32 + acc_row(reg, hf) > q) s[j][reg] = -INFINITY;
       }
-      if (sw.cut(kt, qtile)) window_mask_qlane<NT>(s, kt, q, win, hf);
+      if (sw.cut(kt, qtile)) {
+        if constexpr (BOUNDS) bound_mask_qlane<NT>(s, kt, lo_q, hf);
+        else window_mask_qlane<NT>(s, kt, q, win, hf);
+      }
       // row max on the raw scores (scale > 0); the scale is folded into the
       // exponent's FMA instead of a separate multiply pass
       float tmax = s[0][0];
@@ -644,9 +682,10 @@ __device__ __forceinline__ void unrope(f32x16 (&x)[D / 32], const AttnArgs& a, i
   }
 }
 
-template <int D, bool DROP, int NT>
+template <int D, bool DROP, int NT, bool BOUNDS = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(D == 64 ? DLION_DQ_WAVES64 : 1)))
 attn_bwd_dq_kernel(AttnArgs a) {
+  static_assert(!BOUNDS || (D == 128 && !DROP), "bounds: D = 128 without dropout");
   constexpr int NB = DLION_ATTN_STAGES;
   __shared__ __attribute__((aligned(16))) LdsTile<D> ks_[NB][NT];
   __shared__ __attribute__((aligned(16))) LdsTile<D> vs_[NB][NT];
@@ -657,8 +696,9 @@ attn_bwd_dq_kernel(AttnArgs a) {
   const int b = bh / a.H, h = bh % a.H, hk = h / (a.H / a.Hkv);
   const int q = qtile * 32 + r;
   const int qc = min(q, a.T - 1);  // tail rows: a copy of row T-1, never stored (see the forward)
-  const int win = window_of<D>(a);
-  const SlideRange sw(win, qtile, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), NT);
+  const int win = BOUNDS ? 0 : window_of<D>(a);
+  const SlideRange sw = key_range<BOUNDS>(a, b, win, qtile, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), NT);
+  const int lo_q = BOUNDS ? a.row_lo[static_cast<int64_t>(b) * a.T + qc] : 0;
 
   bf16x8 qf[D / 16], dof[D / 16];
   float lse2 = 0.f, dlt = 0.f;
@@ -752,7 +792,10 @@ attn_bwd_dq_kernel(AttnArgs a) {
           for (int reg = 0; reg < 16; ++reg)
             if ((kt0 + j) * 32 + acc_row(reg, hf) > q) s[j][reg] = -INFINITY;
       }
-      if (sw.cut(kt0, qtile)) window_mask_qlane<NT>(s, kt0, q, win, hf);
+      if (sw.cut(kt0, qtile)) {
+        if constexpr (BOUNDS) bound_mask_qlane<NT>(s, kt0, lo_q, hf);
+        else window_mask_qlane<NT>(s, kt0, q, win, hf);
+      }
 #pragma unroll
       for (int j = 0; j < NT; ++j)
 #pragma unroll
@@ -804,7 +847,7 @@ attn_bwd_dq_kernel(AttnArgs a) {
 // every head in the GQA group is staged once per block (Q, dO and the 32
 // lse / delta values).  Low key groups (most query tiles) go first.  (Round
 // 3's software-pipelined variant measured -1 % and was removed.)
-template <int D, bool DROP, bool KREG = false>
+template <int D, bool DROP, bool KREG = false, bool BOUNDS = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(
     D == 64 ? DLION_DKV_WAVES64 : (KREG ? 2 : DLION_DKV_WAVES128))))
 attn_bwd_dkv_kernel(AttnArgs a) {
@@ -812,6 +855,7 @@ attn_bwd_dkv_kernel(AttnArgs a) {
   __shared__ __attribute__((aligned(16))) LdsTile<D> qs_[NB];
   __shared__ __attribute__((aligned(16))) LdsTile<D> ds_[NB];
   static_assert(!KREG || (D == 128 && !DROP), "K in registers: D = 128 without dropout");  // (see above)
+  static_assert(!BOUNDS || (D == 128 && !DROP), "bounds: D = 128 without dropout");
   constexpr int KV = KREG ? 0 : 1;  // V's slot in kvs_
   __shared__ __attribute__((aligned(16))) LdsTile<D> kvs_[KREG ? 1 : 2][4];  // [K | V][wave's key tile]
   __shared__ __attribute__((aligned(16))) float ls_[NB][6][32];  // [buf][lse | delta | hash base of key tile 0..3][row]
@@ -869,12 +913,26 @@ attn_bwd_dkv_kernel(AttnArgs a) {
   const DmaTile<D> qd(a.q_st), dd(a.o_st);
   // query tiles per head: first .. qhi (a sliding window ends the block's range
   // at the last query its highest key reaches)
-  const int win = window_of<D>(a);
-  const int qhi = win > 0 ? min(ntiles - 1, (first * 32 + 127 + win - 1) >> 5) : ntiles - 1;
+  const int win = BOUNDS ? 0 : window_of<D>(a);
+  int qhi = win > 0 ? min(ntiles - 1, (first * 32 + 127 + win - 1) >> 5) : ntiles - 1;
   // this wave's last in-window query tile, and the first query tile holding a
   // query at or past (lowest key) + window: only those need the element mask
-  const int wq_last = win > 0 ? (kb + 30 + win) >> 5 : ntiles;
-  const int wq_cut = win > 0 ? kb + win - 31 : 1 << 30;
+  int wq_last = win > 0 ? (kb + 30 + win) >> 5 : ntiles;
+  int wq_cut = win > 0 ? kb + win - 31 : 1 << 30;
+  // BOUNDS: the same three from key_hi (non-decreasing) at the block's last
+  // valid key and the wave's last / first key, and the lane's own bound for
+  // the element mask.  Reads are clamped to row T - 1 and the block's range to
+  // [first, ntiles - 1], the only one of the three that bounds an address.
+  int khi = 0;
+  if constexpr (BOUNDS) {
+    const int32_t* kh = a.key_hi + static_cast<int64_t>(b) * a.T;
+    // (readfirstlane: the clamp compiles to a VALU v_med3; qhi is a scalar loop bound)
+    qhi = __builtin_amdgcn_readfirstlane(min(max((kh[min(first * 32 + 127, a.T - 1)] - 1) >> 5, first), ntiles - 1));
+    // wave-uniform loads; readfirstlane makes the two branches they gate scalar by construction
+    wq_last = __builtin_amdgcn_readfirstlane((kh[min(kb + 31, a.T - 1)] - 1) >> 5);
+    wq_cut = __builtin_amdgcn_readfirstlane(kh[min(kb, a.T - 1)] - 31);
+    khi = kh[min(key, a.T - 1)];
+  }
   const int nq = qhi - first + 1;
   const int total = group * nq;    // (head, query tile) steps, head-major
   // step i -> buffer i&1: Q and dO tiles by LDS-DMA; wave 0 also DMAs the 32
@@ -946,8 +1004,9 @@ attn_bwd_dkv_kernel(AttnArgs a) {
         for (int reg = 0; reg < 16; ++reg)
           if (qb + acc_row(reg, hf) >= a.T) s[reg] = -INFINITY;
       }
-      if (D == 128 && qb >= wq_cut) {  // sliding window: queries at or past key + window (window_of<D> reloaded here)
-        const int kw = key + window_of<D>(a);
+      // sliding window: queries at or past key + window (window_of<D> reloaded here); BOUNDS: at or past key_hi[key]
+      if (D == 128 && qb >= wq_cut) {
+        const int kw = BOUNDS ? khi : key + window_of<D>(a);
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg)
           if (qb + acc_row(reg, hf) >= kw) s[reg] = -INFINITY;
@@ -1055,8 +1114,21 @@ attn_bwd_dkv_kernel(AttnArgs a) {
 // ceil(tiles / 4) blocks of 4 waves per head
 static inline int64_t tile_blocks(int64_t nbh, int T) { return nbh * ((((T + 31) >> 5) + 3) >> 2); }
 
+// Per-row bounds come as a pair, at D = 128 without dropout, with the window
+// folded into them by the host, and not with the packed-qkv bias partials
+// (colsum: the GPT-2 path, which has no document isolation).
+static inline bool has_bounds(const AttnArgs& a) { return a.row_lo != nullptr || a.key_hi != nullptr; }
+static inline bool bounds_ok(const AttnArgs& a, int D, bool drop) {
+  return a.row_lo != nullptr && a.key_hi != nullptr && D == 128 && !drop && a.window == 0 && a.colsum == nullptr;
+}
+
 hipError_t launch_attn_fwd(const AttnArgs& a, int D, bool drop, hipStream_t st) {
   const dim3 grid(static_cast<unsigned>(tile_blocks(static_cast<int64_t>(a.B) * a.H, a.T))), block(256);
+  if (has_bounds(a)) {
+    if (!bounds_ok(a, D, drop)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((attn_fwd_kernel<128, false, 1, true>), grid, block, 0, st, a);
+    return hipGetLastError();
+  }
   // NT = 2 key tiles per barrier at D=64 (GPT-2 shape fwd 0.067 -> 0.065 ms);
   // at D=128 the extra 64 VGPRs cost a wave of occupancy and it was neutral
 #define FWD(DD, NT)                                                                        \
@@ -1079,6 +1151,17 @@ static constexpr bool dkv_kreg() { return DLION_DKV_KREG128 != 0; }
 hipError_t launch_attn_bwd(const AttnArgs& a, int D, bool drop, hipStream_t st) {
   const dim3 bq(static_cast<unsigned>(tile_blocks(static_cast<int64_t>(a.B) * a.H, a.T)));
   const dim3 bkv(static_cast<unsigned>(tile_blocks(static_cast<int64_t>(a.B) * a.Hkv, a.T)));
+  // Bounds: H == Hkv takes the K-in-registers dK/dV kernel as the plain path
+  // does (254 of its 256 VGPRs with the lane's key_hi, no spill), GQA the K-in-LDS one.
+  if (has_bounds(a)) {
+    if (!bounds_ok(a, D, drop)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<128, false, 1, true>), bq, dim3(256), 0, st, a);
+    if (a.H == a.Hkv && dkv_kreg())
+      hipLaunchKernelGGL((attn_bwd_dkv_kernel<128, false, true, true>), bkv, dim3(256), 0, st, a);
+    else
+      hipLaunchKernelGGL((attn_bwd_dkv_kernel<128, false, false, true>), bkv, dim3(256), 0, st, a);
+    return hipGetLastError();
+  }
   // dQ first: it also computes delta = rowsum(dO * O), which dKV reads
 #define BWD(DD)                                                                         \
   if (drop) {                                                                           \

@@ -280,10 +280,32 @@ void set_window(dlion::AttnArgs& a, int64_t window, int64_t D) {
   TORCH_CHECK(a.window == 0 || D == 128, "dlion attn: a sliding window needs head_dim 128");
 }
 
+// Per-row key bounds (document-isolated packing; attention.h): int32 [B, T]
+// on q's device, both or neither, with the window folded in by the caller
+// (fused.visibility_bounds).  Their values are the caller's contract; the
+// kernels clamp what they derive from them.
+void set_bounds(dlion::AttnArgs& a, const std::optional<Tensor>& row_lo, const std::optional<Tensor>& key_hi,
+                const Tensor& q) {
+  a.row_lo = a.key_hi = nullptr;
+  if (!row_lo.has_value() && !key_hi.has_value()) return;
+  TORCH_CHECK(row_lo.has_value() && key_hi.has_value(), "dlion attn: row_lo and key_hi come as a pair");
+  TORCH_CHECK(a.window == 0, "dlion attn: bounds replace the window (fold it into them)");
+  TORCH_CHECK(q.size(3) == 128 && a.thresh16 == 0, "dlion attn: bounds need head_dim 128 and no dropout");
+  for (const Tensor* t : {&*row_lo, &*key_hi}) {
+    TORCH_CHECK(t->device() == q.device() && t->scalar_type() == at::kInt && t->is_contiguous() && t->dim() == 2 &&
+                    t->size(0) == q.size(0) && t->size(1) == q.size(1),
+                "dlion attn: row_lo / key_hi must be contiguous int32 [B, T] on the inputs' device");
+  }
+  a.row_lo = row_lo->data_ptr<int32_t>();
+  a.key_hi = key_hi->data_ptr<int32_t>();
+}
+
 std::tuple<Tensor, Tensor> attn_fwd(const Tensor& q, const Tensor& k, const Tensor& v, double p, int64_t seed,
-                                    int64_t window) {
+                                    int64_t window, const std::optional<Tensor>& row_lo,
+                                    const std::optional<Tensor>& key_hi) {
   auto a = attn_args(q, k, v, p, seed);
   set_window(a, window, q.size(3));
+  set_bounds(a, row_lo, key_hi, q);
   const c10::DeviceGuard g(q.device());
   auto out = at::empty({q.size(0), q.size(1), q.size(2), q.size(3)}, q.options());
   auto lse = at::empty({q.size(0), q.size(2), q.size(1)}, q.options().dtype(at::kFloat));
@@ -297,9 +319,12 @@ std::tuple<Tensor, Tensor> attn_fwd(const Tensor& q, const Tensor& k, const Tens
 void attn_bwd(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& out, const Tensor& dout,
               const Tensor& lse, double p, int64_t seed, const Tensor& dq, const Tensor& dk, const Tensor& dv,
               const std::optional<Tensor>& colsum, const std::optional<Tensor>& rope_cos,
-              const std::optional<Tensor>& rope_sin, int64_t window) {
+              const std::optional<Tensor>& rope_sin, int64_t window, const std::optional<Tensor>& row_lo,
+              const std::optional<Tensor>& key_hi) {
   auto a = attn_args(q, k, v, p, seed);
   set_window(a, window, q.size(3));
+  set_bounds(a, row_lo, key_hi, q);
+  TORCH_CHECK(a.row_lo == nullptr || !colsum.has_value(), "dlion attn: bounds do not go with bias-gradient partials");
   check_bthd(out, "out");
   check_bthd(dout, "dout");
   check_bthd(dq, "dq");
@@ -1241,11 +1266,12 @@ TORCH_LIBRARY(dlion, m) {
   m.def("sum_partials_scaled_(Tensor part, Tensor s, Tensor(a!) out, bool accumulate) -> ()");
   m.def("sum_partials_multi_(Tensor[] parts, Tensor(a!) out, bool accumulate) -> ()");
   m.def("colsum_partials(Tensor x, int parts) -> Tensor");
-  m.def("attn_fwd(Tensor q, Tensor k, Tensor v, float p, int seed, int window=0) -> (Tensor, Tensor)");
+  m.def("attn_fwd(Tensor q, Tensor k, Tensor v, float p, int seed, int window=0, Tensor? row_lo=None,"
+        " Tensor? key_hi=None) -> (Tensor, Tensor)");
   m.def(
       "attn_bwd(Tensor q, Tensor k, Tensor v, Tensor out, Tensor dout, Tensor lse, float p, int seed,"
       " Tensor(a!) dq, Tensor(b!) dk, Tensor(c!) dv, Tensor(d!)? colsum=None, Tensor? rope_cos=None,"
-      " Tensor? rope_sin=None, int window=0) -> ()");
+      " Tensor? rope_sin=None, int window=0, Tensor? row_lo=None, Tensor? key_hi=None) -> ()");
   m.def("softmax_xent_(Tensor(a!) logits, Tensor labels, int v, int variant=0) -> Tensor");
   m.def(
       "lion_local(Tensor meta, int seg_off, int chunk_off, int n_chunks, int dtype, float decay, float neg_lr,"

@@ -153,13 +153,14 @@ class LlamaAttention(nn.Module):
         self.o_proj = nn.Linear(self.n_head * self.head_dim, cfg.hidden_size, bias=o_bias)
         self.attn_dropout = float(getattr(cfg, "attention_dropout", 0.0) or 0.0)
 
-    def forward(self, x, cos, sin):
+    def forward(self, x, cos, sin, bounds=None):
         B, T, _ = x.shape
         q, k, v = _proj(x, (self.q_proj, self.k_proj, self.v_proj))
         q = q.view(B, T, self.n_head, self.head_dim)
         k = k.view(B, T, self.n_kv, self.head_dim)
         v = v.view(B, T, self.n_kv, self.head_dim)
-        y = fused.rope_attention(q, k, v, cos, sin, self.attn_dropout if self.training else 0.0, self.window)
+        y = fused.rope_attention(q, k, v, cos, sin, self.attn_dropout if self.training else 0.0, self.window,
+                                 bounds)
         return _lin(self.o_proj, y)
 
 
@@ -224,8 +225,8 @@ class LlamaDecoderLayer(nn.Module):
         self.input_layernorm = RMSNorm(cfg.hidden_size, cfg.rms_norm_eps)
         self.post_attention_layernorm = RMSNorm(cfg.hidden_size, cfg.rms_norm_eps)
 
-    def forward(self, x, cos, sin):
-        x = x + self.self_attn(self.input_layernorm(x), cos, sin)
+    def forward(self, x, cos, sin, bounds=None):
+        x = x + self.self_attn(self.input_layernorm(x), cos, sin, bounds)
         return x + self.mlp(self.post_attention_layernorm(x))
 
 
@@ -239,21 +240,41 @@ class LlamaModel(nn.Module):
         self.rotary = Rotary(head_dim, _rope_theta(cfg))
         self.gradient_checkpointing = False
 
-    def forward(self, input_ids):
+    def _visibility(self, position_ids):
+        """Per-layer attention bounds of document-isolated packing (None without
+        position_ids): fused.visibility_bounds once per distinct layer window
+        (Mistral: one; Qwen2 sliding configs: two), shared by the layers."""
+        if position_ids is None:
+            return [None] * len(self.layers)
+        per_window = {}
+        for layer in self.layers:
+            w = layer.self_attn.window
+            if w not in per_window:
+                per_window[w] = fused.visibility_bounds(position_ids, w)
+        return [per_window[layer.self_attn.window] for layer in self.layers]
+
+    def forward(self, input_ids, position_ids=None):
         T = input_ids.shape[1]
         x = self.embed_tokens(input_ids)
+        # position_ids that restart per document (packed rows) bound every row's
+        # keys to its own document.  The rotary tables stay indexed by the global
+        # position t: a score depends on pos_q - pos_k only, and inside a document
+        # global and per-document positions differ by the same offset for q and k,
+        # so both give the same attention in exact arithmetic -- no second table,
+        # no gather, and the backward's inverse rotation is unchanged.
         cos, sin = self.rotary.tables(T, x.device, x.dtype)
+        bounds = self._visibility(position_ids)
         if self.gradient_checkpointing and self.training:
             no_wgrad_deferral_this_window()  # keep checkpointing's memory saving (ops/linear.py)
-            for layer in self.layers:
-                x = torch.utils.checkpoint.checkpoint(layer, x, cos, sin, use_reentrant=False)
+            for layer, bd in zip(self.layers, bounds):
+                x = torch.utils.checkpoint.checkpoint(layer, x, cos, sin, bd, use_reentrant=False)
             return self.norm(x)
         # fused path: each "residual add + next RMSNorm" is one kernel
         first = self.layers[0].input_layernorm
         h = fused.norm(x, first.weight, None, first.eps, rms=True)
         for i, layer in enumerate(self.layers):
             pn = layer.post_attention_layernorm
-            x, h = fused.dropout_add_norm(layer.self_attn(h, cos, sin), x, pn.weight, None, pn.eps, 0.0, rms=True)
+            x, h = fused.dropout_add_norm(layer.self_attn(h, cos, sin, bounds[i]), x, pn.weight, None, pn.eps, 0.0, rms=True)
             nxt = self.layers[i + 1].input_layernorm if i + 1 < len(self.layers) else self.norm
             x, h = fused.dropout_add_norm(layer.mlp(h), x, nxt.weight, None, nxt.eps, 0.0, rms=True)
         return h
@@ -309,8 +330,10 @@ class LlamaForCausalLM(PreTrainedModel):
         self.model.gradient_checkpointing = False
 
     def forward(self, input_ids=None, labels=None, attention_mask=None, num_items_in_batch=None,
-                return_dict: Optional[bool] = None, **kwargs):
-        h = self.model(input_ids)
+                return_dict: Optional[bool] = None, position_ids=None, **kwargs):
+        # position_ids is a named parameter: HF's remove_unused_columns keeps only
+        # those.  They switch on document-isolated attention (LlamaModel.forward).
+        h = self.model(input_ids, position_ids)
         loss = logits = None
         if labels is not None:
             loss = fused.causal_lm_loss(h, self.lm_head.weight, labels, normalizer=num_items_in_batch)

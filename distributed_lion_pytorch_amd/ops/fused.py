@@ -548,7 +548,7 @@ def mlp_gelu(x: torch.Tensor, w_fc: torch.Tensor, b_fc: torch.Tensor, w_proj: to
 # OR a bit into a per-device int32 flag, which check_index_errors() reads
 # once per optimizer step without stalling the stream (one step late) or, at
 # the end of a run, synchronously.
-_IDX_EMBED, _IDX_LABEL = 1, 2
+_IDX_EMBED, _IDX_LABEL, _IDX_POS = 1, 2, 4
 _IDX_FLAGS: dict = {}  # device -> [flag int32[1] (device), pinned host mirror, copy-done event]
 
 
@@ -567,6 +567,8 @@ def _index_error(code: int, where: str):
                     "the model vocabulary? (run_clm resizes the embeddings for that)")
     if code & _IDX_LABEL:
         msgs.append("a label is outside [0, vocab_size) and is not the ignore index -100")
+    if code & _IDX_POS:
+        msgs.append(_POS_MSG)
     return ValueError(f"dlion ({where}): " + "; ".join(msgs))
 
 
@@ -668,12 +670,59 @@ def embed(ids: torch.Tensor, wte: torch.Tensor, wpe: torch.Tensor, p: float) -> 
 
 
 # ------------------------------------------------------------------ attention
-def _attn_ok(x: torch.Tensor, T: int, D: int, window: int = 0) -> bool:
+def _attn_ok(x: torch.Tensor, T: int, D: int, window: int = 0, bounds=None, dropout_p: float = 0.0) -> bool:
     """The gfx950 flash kernels take any sequence length (tail tiles are
     masked in-kernel) at head_dim 64 / 128 -- every GPT-2 and Llama-2/3 size;
-    a sliding window (< T) at head_dim 128 (csrc/attention.hip window_of)."""
+    a sliding window (< T) at head_dim 128 (csrc/attention.hip window_of);
+    per-row bounds at head_dim 128 without dropout (the BOUNDS instantiations)."""
     return (x.dtype == torch.bfloat16 and D in (64, 128) and T >= 1 and _use_hip(x)
-            and (_eff_window(window, T) == 0 or D == 128))
+            and (_eff_window(window, T) == 0 or D == 128)
+            and (bounds is None or (D == 128 and dropout_p == 0)))
+
+
+_POS_MSG = ("position_ids must increase by one inside a document (a document starts at t = 0 and wherever "
+            "position_ids == 0)")
+
+
+def visibility_bounds(position_ids: torch.Tensor, window: int = 0):
+    """(row_lo, key_hi), int32 [B, T]: the per-row key bounds of document-
+    isolated causal attention over packed rows.  A document starts at t = 0
+    and wherever ``position_ids[b, t] == 0``; query q sees keys
+    ``row_lo[q] <= k <= q`` and key k is seen by queries ``k <= q < key_hi[k]``:
+    row_lo = max(start of q's document, q - window + 1), key_hi = min(start of
+    the next document or T, k + window), the window applied when 0 < window < T
+    -- so the kernels need no window beside the bounds.  Both are non-decreasing
+    along T.  Built on the input's device without a host sync.  Inside a
+    document position_ids must step by one: a CPU tensor is checked here
+    (ValueError), a CUDA one through the per-step index flag
+    (check_index_errors, one step late, like token ids)."""
+    pos = position_ids if position_ids.dim() == 2 else position_ids.reshape(1, -1)
+    B, T = pos.shape
+    idx = torch.arange(T, device=pos.device, dtype=torch.int64).expand(B, T)
+    start = pos == 0
+    start[:, 0] = True
+    bad = (~start[:, 1:] & (pos[:, 1:] != pos[:, :-1] + 1)).any()
+    if pos.is_cuda:
+        _index_flag(pos.device).bitwise_or_(bad.to(torch.int32) * _IDX_POS)
+    elif bool(bad):
+        raise ValueError("dlion (position_ids): " + _POS_MSG)
+    row_lo = torch.where(start, idx, torch.zeros_like(idx)).cummax(dim=1).values
+    # the first document start after k: a flipped running minimum over the starts at k + 1 ..
+    nxt = torch.where(start, idx, torch.full_like(idx, T))
+    nxt = torch.cat([nxt[:, 1:], torch.full_like(idx[:, :1], T)], dim=1)
+    key_hi = nxt.flip(1).cummin(dim=1).values.flip(1)
+    w = int(window or 0)
+    if 0 < w < T:
+        row_lo = torch.maximum(row_lo, idx - (w - 1))
+        key_hi = torch.minimum(key_hi, idx + w)
+    return row_lo.to(torch.int32).contiguous(), key_hi.to(torch.int32).contiguous()
+
+
+def _bounds_mask(bounds, T: int) -> torch.Tensor:
+    """bool [B, 1, T(q), T(key)]: row_lo[q] <= key <= q."""
+    row_lo = bounds[0]
+    i = torch.arange(T, device=row_lo.device)
+    return ((i[None, None, :] >= row_lo[:, :, None]) & (i[None, None, :] <= i[None, :, None]))[:, None]
 
 
 def _eff_window(window, T: int) -> int:
@@ -684,24 +733,31 @@ def _eff_window(window, T: int) -> int:
 _MATH_WARNED = set()
 
 
-def _sdpa_math(q, k, v, dropout_p: float, window: int = 0) -> torch.Tensor:
+def _sdpa_math(q, k, v, dropout_p: float, window: int = 0, bounds=None) -> torch.Tensor:
     """Fallback for what the flash kernels do not cover (head_dim not in {64,
-    128}, fp32/fp16 inputs, no extension): PyTorch's *math* SDPA backend only
+    128}, fp32/fp16 inputs, no extension; per-row ``bounds`` at head_dim 64 or
+    with dropout): PyTorch's *math* SDPA backend only
     -- matmul + softmax ATen ops (hipBLASLt GEMMs) -- never the flash /
     memory-efficient backends, which on ROCm are Triton-built (aotriton).
     O(T^2) memory; a one-time warning names the shape."""
     from torch.nn.attention import SDPBackend, sdpa_kernel
 
-    key = (tuple(q.shape[-2:]), q.dtype, q.device.type)
+    # per-row bounds have a flash kernel only at head_dim 128 without dropout: a
+    # shape the plain kernels cover can still land here, so the key and the
+    # message say what was asked for
+    what = "" if bounds is None else (" with per-row bounds and dropout" if dropout_p > 0 else " with per-row bounds")
+    key = (tuple(q.shape[-2:]), q.dtype, q.device.type, what)
     if q.is_cuda and key not in _MATH_WARNED:
         _MATH_WARNED.add(key)
         import warnings
 
-        warnings.warn(f"dlion attention: no gfx950 flash kernel for head_dim={q.shape[-1]} / {q.dtype}; "
+        warnings.warn(f"dlion attention: no gfx950 flash kernel for head_dim={q.shape[-1]} / {q.dtype}{what}; "
                       "using the math SDPA backend (O(T^2) memory)")
     T = q.shape[-2]
     window = _eff_window(window, T)
     with sdpa_kernel([SDPBackend.MATH]):
+        if bounds is not None:  # the window is folded into the bounds (visibility_bounds)
+            return F.scaled_dot_product_attention(q, k, v, attn_mask=_bounds_mask(bounds, T), dropout_p=dropout_p)
         if window:  # HF's sliding-window mask: key k visible to query q iff q - window < k <= q
             i = torch.arange(T, device=q.device)
             d = i[:, None] - i[None, :]
@@ -739,21 +795,22 @@ class _FlashAttn(torch.autograd.Function):
     """Causal (GQA) attention on separate q [B,T,H,D], k/v [B,T,Hkv,D]."""
 
     @staticmethod
-    def forward(ctx, q, k, v, p, seed, window=0):
-        out, lse = hip.ops().attn_fwd(q, k, v, p, seed, window)
-        ctx.save_for_backward(q, k, v, out, lse)
+    def forward(ctx, q, k, v, p, seed, window=0, bounds=None):
+        row_lo, key_hi = bounds if bounds is not None else (None, None)
+        out, lse = hip.ops().attn_fwd(q, k, v, p, seed, window, row_lo, key_hi)
+        ctx.save_for_backward(q, k, v, out, lse, row_lo, key_hi)
         ctx.p, ctx.seed, ctx.window = p, seed, window
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        q, k, v, out, lse = ctx.saved_tensors
+        q, k, v, out, lse, row_lo, key_hi = ctx.saved_tensors
         dout = dout.contiguous()
         dq = torch.empty(q.shape, dtype=q.dtype, device=q.device)
         dkv = torch.empty((2,) + tuple(k.shape), dtype=k.dtype, device=k.device)
         hip.ops().attn_bwd(q, k, v, out, dout, lse, ctx.p, ctx.seed, dq, dkv[0], dkv[1], None, None, None,
-                           ctx.window)
-        return dq, dkv[0], dkv[1], None, None, None
+                           ctx.window, row_lo, key_hi)
+        return dq, dkv[0], dkv[1], None, None, None, None
 
 
 def causal_attention(qkv: torch.Tensor, dropout_p: float) -> torch.Tensor:
@@ -843,25 +900,39 @@ def qkv_attention(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, n_head: int
     return causal_attention(qkv, dropout_p)
 
 
+def _check_bounds(bounds, B: int, T: int):
+    """(row_lo, key_hi) of visibility_bounds for this [B, T] batch, or None."""
+    if bounds is None:
+        return None
+    row_lo, key_hi = bounds
+    if tuple(row_lo.shape) != (B, T) or tuple(key_hi.shape) != (B, T):
+        raise ValueError(f"attention bounds must be [B, T] = [{B}, {T}], got {tuple(row_lo.shape)} / {tuple(key_hi.shape)}")
+    return row_lo, key_hi
+
+
 def causal_attention_gqa(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, dropout_p: float = 0.0,
-                         window: int = 0) -> torch.Tensor:
+                         window: int = 0, bounds=None) -> torch.Tensor:
     """q [B,T,H,D], k/v [B,T,Hkv,D] -> [B,T,H*D] (grouped-query causal attention;
-    ``window`` > 0: sliding window, query q sees keys q - window < k <= q)."""
+    ``window`` > 0: sliding window, query q sees keys q - window < k <= q).
+    ``bounds`` = visibility_bounds(position_ids, window): per-row key bounds of
+    document-isolated packing; they hold the window, which is then not applied
+    a second time."""
     B, T, H, D = q.shape
-    window = _eff_window(window, T)
+    bounds = _check_bounds(bounds, B, T)
+    window = 0 if bounds is not None else _eff_window(window, T)
     if q.is_cuda:
         from .linear import autocast_inputs
 
         q, k, v = autocast_inputs(q, k, v)
-    if _attn_ok(q, T, D, window):
+    if _attn_ok(q, T, D, window, bounds, dropout_p):
         with torch.autocast("cuda", enabled=False):
-            return _FlashAttn.apply(q, k, v, float(dropout_p), _new_seed(), window).view(B, T, H * D)
+            return _FlashAttn.apply(q, k, v, float(dropout_p), _new_seed(), window, bounds).view(B, T, H * D)
     rep = H // k.shape[2]
     qh, kh, vh = q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2)
     if rep > 1:
         kh = kh.repeat_interleave(rep, dim=1)
         vh = vh.repeat_interleave(rep, dim=1)
-    y = _sdpa_math(qh, kh, vh, dropout_p, window)
+    y = _sdpa_math(qh, kh, vh, dropout_p, window, bounds)
     return y.transpose(1, 2).reshape(B, T, H * D)
 
 
@@ -888,7 +959,7 @@ class _RopeAttention(torch.autograd.Function):
     Llama-2-7B LoRA SFT step)."""
 
     @staticmethod
-    def forward(ctx, q, k, v, cos, sin, p, seed, window=0):
+    def forward(ctx, q, k, v, cos, sin, p, seed, window=0, bounds=None):
         ops = hip.ops()
         H = q.shape[2]
         qk = _adjacent_heads(q, k)
@@ -898,14 +969,15 @@ class _RopeAttention(torch.autograd.Function):
         else:
             qr = ops.rope(q, cos, sin, False)
             kr = ops.rope(k, cos, sin, False)
-        out, lse = ops.attn_fwd(qr, kr, v, p, seed, window)
-        ctx.save_for_backward(qr, kr, v, out, lse, cos, sin)
+        row_lo, key_hi = bounds if bounds is not None else (None, None)
+        out, lse = ops.attn_fwd(qr, kr, v, p, seed, window, row_lo, key_hi)
+        ctx.save_for_backward(qr, kr, v, out, lse, cos, sin, row_lo, key_hi)
         ctx.p, ctx.seed, ctx.window = p, seed, window
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        qr, kr, v, out, lse, cos, sin = ctx.saved_tensors
+        qr, kr, v, out, lse, cos, sin, row_lo, key_hi = ctx.saved_tensors
         B, T, H, D = qr.shape
         Hkv = kr.shape[2]
         buf = torch.empty(B, T, H + 2 * Hkv, D, dtype=qr.dtype, device=qr.device)
@@ -914,34 +986,35 @@ class _RopeAttention(torch.autograd.Function):
         if _ROPE_BWD_FUSED and cos.shape[-1] == D:
             # the kernels store dq / dk through the inverse rotation (no extra pass)
             ops.attn_bwd(qr, kr, v, out, dout.contiguous(), lse, ctx.p, ctx.seed, dq, dk, dv, None,
-                         cos.reshape(-1, D), sin.reshape(-1, D), ctx.window)
-            return dq, dk, dv, None, None, None, None, None
+                         cos.reshape(-1, D), sin.reshape(-1, D), ctx.window, row_lo, key_hi)
+            return dq, dk, dv, None, None, None, None, None, None
         ops.attn_bwd(qr, kr, v, out, dout.contiguous(), lse, ctx.p, ctx.seed, dq, dk, dv, None, None, None,
-                     ctx.window)
+                     ctx.window, row_lo, key_hi)
         ops.rope_(buf[:, :, :H + Hkv], cos, sin, True)  # dq | dk: one in-place inverse rotation
-        return dq, dk, dv, None, None, None, None, None
+        return dq, dk, dv, None, None, None, None, None, None
 
 
 _ROPE_BWD_FUSED = True  # inverse rotation in the bwd kernels' stores (tests compare the separate pass)
 
 
 def rope_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
-                   dropout_p: float = 0.0, window: int = 0) -> torch.Tensor:
-    """causal_attention_gqa(rope(q), rope(k), v, window) -> [B, T, H*D]; q [B,T,H,D],
+                   dropout_p: float = 0.0, window: int = 0, bounds=None) -> torch.Tensor:
+    """causal_attention_gqa(rope(q), rope(k), v, window, bounds) -> [B, T, H*D]; q [B,T,H,D],
     k / v [B,T,Hkv,D] (views of a fused projection output are read in place)."""
     B, T, H, D = q.shape
-    window = _eff_window(window, T)
+    bounds = _check_bounds(bounds, B, T)
+    window = 0 if bounds is not None else _eff_window(window, T)
     if q.is_cuda:
         from .linear import autocast_inputs
 
         q, k, v = autocast_inputs(q, k, v)
-    if (_attn_ok(q, T, D, window) and cos.dtype == sin.dtype == torch.bfloat16
+    if (_attn_ok(q, T, D, window, bounds, dropout_p) and cos.dtype == sin.dtype == torch.bfloat16
             and k.dtype == v.dtype == torch.bfloat16 and all(_token_strided_ok(t) for t in (q, k, v))):
         with torch.autocast("cuda", enabled=False):
             out = _RopeAttention.apply(q, k, v, cos.contiguous(), sin.contiguous(), float(dropout_p), _new_seed(),
-                                       window)
+                                       window, bounds)
         return out.view(B, T, H * D)
-    return causal_attention_gqa(rope(q, cos, sin), rope(k, cos, sin), v, dropout_p, window)
+    return causal_attention_gqa(rope(q, cos, sin), rope(k, cos, sin), v, dropout_p, window, bounds)
 
 
 # ------------------------------------------------------------------- LoRA
@@ -1069,9 +1142,10 @@ def attention_dropout_keep(B: int, H: int, T: int, p: float, seed: int, device=N
     return (s16 >= th - 32768).view(B, H, T, T)
 
 
-def reference_attention(q, k, v, dropout_p: float = 0.0, seed: int = 0, window: int = 0) -> torch.Tensor:
+def reference_attention(q, k, v, dropout_p: float = 0.0, seed: int = 0, window: int = 0, bounds=None) -> torch.Tensor:
     """fp32 math reference with the kernels' dropout mask: q [B,T,H,D], k/v [B,T,Hkv,D]
-    (``window`` > 0: keys q - window < k <= q only)."""
+    (``window`` > 0: keys q - window < k <= q only; ``bounds``: keys row_lo[q] <= k <= q,
+    the window already inside them)."""
     B, T, H, D = q.shape
     rep = H // k.shape[2]
     qh = q.float().transpose(1, 2)
@@ -1079,7 +1153,9 @@ def reference_attention(q, k, v, dropout_p: float = 0.0, seed: int = 0, window: 
     vh = v.float().transpose(1, 2).repeat_interleave(rep, dim=1)
     s = (qh @ kh.transpose(-1, -2)) / (D ** 0.5)
     causal = torch.ones(T, T, dtype=torch.bool, device=q.device).tril()
-    if window:
+    if bounds is not None:
+        causal = _bounds_mask(bounds, T)
+    elif window:
         causal &= ~torch.ones(T, T, dtype=torch.bool, device=q.device).tril(-window)
     s = s.masked_fill(~causal, float("-inf"))
     pr = torch.softmax(s, dim=-1)

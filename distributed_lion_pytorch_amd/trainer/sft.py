@@ -32,15 +32,21 @@ class SFTTrainer(RankShardedLoaderMixin, Trainer):
     def __init__(self, model=None, args=None, train_dataset=None, eval_dataset=None, tokenizer=None,
                  processing_class=None, peft_config: Optional[LoraConfig] = None, packing: bool = True,
                  max_seq_length: int = 1024, formatting_func: Optional[Callable] = None, data_collator=None,
-                 **kwargs):
+                 isolate_documents: bool = False, **kwargs):
+        # isolate_documents: the datasets packed here carry position_ids that restart
+        # per sample (utils/data.isolated_item); the native Llama-family models turn
+        # them into document-isolated attention.  Datasets that come in packed keep
+        # what their builder chose.
         tok = processing_class if processing_class is not None else tokenizer
         if peft_config is not None:
             inject_lora(model, peft_config)
         fmt = formatting_func or prepare_sample_text
         if packing and not _is_packed(train_dataset):
-            train_dataset = ConstantLengthDataset(tok, train_dataset, fmt, seq_length=max_seq_length)
+            train_dataset = ConstantLengthDataset(tok, train_dataset, fmt, seq_length=max_seq_length,
+                                                  isolate_documents=isolate_documents)
         if packing and not _is_packed(eval_dataset):
-            eval_dataset = ConstantLengthDataset(tok, eval_dataset, fmt, seq_length=max_seq_length)
+            eval_dataset = ConstantLengthDataset(tok, eval_dataset, fmt, seq_length=max_seq_length,
+                                                 isolate_documents=isolate_documents)
         super().__init__(model=model, args=args, train_dataset=train_dataset, eval_dataset=eval_dataset,
                          processing_class=tok, data_collator=data_collator or default_data_collator, **kwargs)
 

@@ -491,29 +491,56 @@ def prepare_sample_text(example: Dict[str, str]) -> str:
     return f"Question: {example['question']}\n\nAnswer: {example['response_j']}"
 
 
+def isolated_item(ids: torch.Tensor, pos: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """One packed block with document isolation: ``pos`` holds each token's
+    index inside its sample (the joining EOS is its sample's last token).  A
+    block that begins mid-sample starts at 0 -- what it holds of that sample is
+    a document of its own -- and ``labels`` are -100 at every document's first
+    token: nothing the model may see predicts it (the previous document's EOS
+    would otherwise be trained to predict the next BOS)."""
+    pos = pos.clone()
+    starts = (pos == 0).nonzero().flatten()
+    lead = int(starts[0]) if len(starts) else len(pos)  # tokens of the sample cut by the block start
+    pos[:lead] -= pos[0].clone()
+    labels = ids.clone()
+    labels[pos == 0] = -100
+    return {"input_ids": ids, "labels": labels, "position_ids": pos}
+
+
 class ConstantLengthDataset(Dataset):
     """Packed fixed-length training chunks (trl ConstantLengthDataset semantics,
     sft_llama2.py:122-129): samples are formatted, tokenized (with the
     tokenizer's special tokens, trl's default), joined with EOS
     and cut into ``seq_length`` blocks.  Map-style (pre-packed once), so every
-    rank reads its own shard instead of rank 0 broadcasting each batch."""
+    rank reads its own shard instead of rank 0 broadcasting each batch.
+    ``isolate_documents``: items also carry ``position_ids`` that restart per
+    sample and ``labels`` masked at sample starts (isolated_item); the
+    ``input_ids`` are the same either way."""
 
     def __init__(self, tokenizer, dataset: Sequence[Dict], formatting_func=prepare_sample_text,
-                 seq_length: int = 1024, eos_token_id: Optional[int] = None):
+                 seq_length: int = 1024, eos_token_id: Optional[int] = None, isolate_documents: bool = False):
         eos = tokenizer.eos_token_id if eos_token_id is None else eos_token_id
         toks: List[int] = []
+        pos: List[int] = []
         for ex in dataset:
-            toks.extend(tokenizer(formatting_func(ex), add_special_tokens=True)["input_ids"])
+            sample = tokenizer(formatting_func(ex), add_special_tokens=True)["input_ids"]
+            toks.extend(sample)
             toks.append(eos)
+            if isolate_documents:
+                pos.extend(range(len(sample) + 1))
         n = max(1, len(toks) // seq_length)
         if len(toks) < seq_length:
-            toks = (toks * (seq_length // max(1, len(toks)) + 1))
+            rep = seq_length // max(1, len(toks)) + 1
+            toks, pos = toks * rep, pos * rep
         self.data = torch.tensor(toks[: n * seq_length], dtype=torch.long).view(n, seq_length)
+        self.pos = torch.tensor(pos[: n * seq_length], dtype=torch.long).view(n, seq_length) if isolate_documents else None
 
     def __len__(self):
         return self.data.shape[0]
 
     def __getitem__(self, i):
+        if self.pos is not None:
+            return isolated_item(self.data[i], self.pos[i])
         return {"input_ids": self.data[i], "labels": self.data[i].clone()}
 
 
@@ -632,13 +659,15 @@ class PackedStream(torch.utils.data.IterableDataset):
     tokens (trl's ``add_special_tokens=True``: a BOS per sample for Llama),
     then joined with EOS.  An infinite stream whose rank shard holds no rows
     (fewer rows than ranks) raises instead of ending: that rank would stop
-    training while the others block in the vote collectives."""
+    training while the others block in the vote collectives.
+    ``isolate_documents``: as in ConstantLengthDataset (isolated_item)."""
 
     rank_sharded = True
 
     def __init__(self, tokenizer, rows, formatting_func=prepare_sample_text, seq_length: int = 1024,
                  infinite: bool = False, chars_per_token: float = 3.6, num_of_sequences: int = 1024,
-                 eos_token_id: Optional[int] = None, shard: bool = True):
+                 eos_token_id: Optional[int] = None, shard: bool = True, isolate_documents: bool = False):
+        self.isolate_documents = isolate_documents
         self.tok, self.rows, self.fmt = tokenizer, rows, formatting_func
         self.seq_length, self.infinite = seq_length, infinite
         self.max_buffer_size = int(seq_length * chars_per_token * num_of_sequences)
@@ -682,12 +711,18 @@ class PackedStream(torch.utils.data.IterableDataset):
             if not buf:
                 break
             ids: List[int] = []
+            pos: List[int] = []
             for t in self.tok(buf, add_special_tokens=True)["input_ids"]:
                 ids.extend(t)
                 ids.append(self.eos)
+                if self.isolate_documents:
+                    pos.extend(range(len(t) + 1))
             for i in range(0, len(ids) - self.seq_length + 1, self.seq_length):
                 x = torch.tensor(ids[i:i + self.seq_length], dtype=torch.long)
-                yield {"input_ids": x, "labels": x.clone()}
+                if self.isolate_documents:
+                    yield isolated_item(x, torch.tensor(pos[i:i + self.seq_length], dtype=torch.long))
+                else:
+                    yield {"input_ids": x, "labels": x.clone()}
 
 
 # ---------------------------------------------------------------- DPO data

@@ -84,6 +84,10 @@ class ScriptArguments:
     load_in_4bit: Optional[bool] = field(default=False, metadata={
         "help": "frozen base weights in 4-bit (the reference's BitsAndBytesConfig, sft_llama2.py:141-145)"})
     bnb_4bit_quant_type: Optional[str] = field(default="nf4", metadata={"help": "nf4 | fp4"})
+    isolate_documents: Optional[bool] = field(default=False, metadata={
+        "help": "packed samples attend only to themselves: position_ids restart per sample and the native "
+                "Llama-family models bound every row's keys to its own sample (default off: the reference's "
+                "packing, where a token also sees the samples packed in front of it)"})
     final_save: Optional[bool] = field(default=True, metadata={
         "help": "save the trained model / adapter at the end (false: throughput runs of 7B models)"})
 
@@ -153,8 +157,9 @@ def create_datasets(tokenizer, script_args, seed):
     ratio = chars_token_ratio(train_rows, tokenizer)
     logger.info(f"The character to token ratio of the dataset is: {ratio:.2f}")
     train = PackedStream(tokenizer, train_rows, prepare_sample_text, seq_length=script_args.seq_length,
-                         infinite=True, chars_per_token=ratio)
-    valid = ConstantLengthDataset(tokenizer, valid_rows, prepare_sample_text, seq_length=script_args.seq_length)
+                         infinite=True, chars_per_token=ratio, isolate_documents=script_args.isolate_documents)
+    valid = ConstantLengthDataset(tokenizer, valid_rows, prepare_sample_text, seq_length=script_args.seq_length,
+                                  isolate_documents=script_args.isolate_documents)
     return train, valid
 
 
@@ -176,6 +181,14 @@ def main(argv=None):
 
     tokenizer = load_tokenizer(script_args.model_name)
     model = build_base(script_args, training_args.seed)
+    if script_args.isolate_documents:
+        from distributed_lion_pytorch_amd.models.llama import LlamaForCausalLM
+
+        if not isinstance(model, LlamaForCausalLM):
+            # another model would drop or misread the position_ids and train with cross-sample attention
+            raise ValueError(f"--isolate_documents needs a native Llama-family model (llama, mistral, qwen2); "
+                             f"{type(model).__module__}.{type(model).__name__} (model_type "
+                             f"{model.config.model_type!r}) does not isolate packed samples")
     if script_args.load_in_4bit:
         from distributed_lion_pytorch_amd.models.quant import QuantConfig, quantize_model
 
@@ -205,6 +218,7 @@ def main(argv=None):
     trainer_class = AsyncSFTTrainer if script_args.async_grad else SFTTrainer
     trainer = trainer_class(model=model, train_dataset=train_dataset, eval_dataset=eval_dataset, peft_config=None,
                             packing=script_args.packing, max_seq_length=script_args.seq_length, tokenizer=tokenizer,
+                            isolate_documents=script_args.isolate_documents,
                             args=training_args, optimizers=(optimizer, sched),
                             callbacks=[JsonlMetricsCallback(training_args.output_dir, script_args.seq_length)])
     warn_unsynced(training_args)
