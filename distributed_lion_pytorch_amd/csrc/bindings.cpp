@@ -735,6 +735,86 @@ void rope_(const Tensor& x, const Tensor& cos, const Tensor& sin, bool inverse) 
             "rope_");
 }
 
+// per-head RMSNorm + rope (csrc/qk_norm.hip): the layout rules of rope; heads
+// [0, split) take gamma_a, heads [split, H) gamma_b (absent: split == H)
+// the stride between the B T token rows of [B, T, H, D]: that of dim 1, or of dim 0 where T == 1 (the stride
+// of a size-1 dimension is arbitrary)
+int64_t qk_token_stride(const Tensor& x) { return x.size(1) == 1 && x.size(0) > 1 ? x.stride(0) : x.stride(1); }
+bool qk_token_strided(const Tensor& x) {
+  const int64_t B = x.size(0), T = x.size(1), D = x.size(3);
+  return x.stride(3) == 1 && (x.size(2) == 1 || x.stride(2) == D) &&
+         (B == 1 || T == 1 || x.stride(0) == T * x.stride(1)) && qk_token_stride(x) % 8 == 0 &&
+         reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0;
+}
+
+void check_qk_norm(const char* what, const Tensor& x, const Tensor& gamma_a, const std::optional<Tensor>& gamma_b,
+                   int64_t split, const Tensor* cos, const Tensor* sin) {
+  TORCH_CHECK(x.dim() == 4 && x.is_cuda() && x.scalar_type() == at::kBFloat16, "dlion ", what,
+              ": x must be bf16 [B, T, H, D]");
+  const int64_t B = x.size(0), T = x.size(1), H = x.size(2), D = x.size(3);
+  TORCH_CHECK(qk_token_strided(x), "dlion ", what,
+              ": x must have contiguous heads and a uniform, 16-byte aligned token stride");
+  TORCH_CHECK(D == 64 || D == 128, "dlion ", what, ": head_dim must be 64 or 128");
+  TORCH_CHECK(split >= 0 && split <= H && (gamma_b.has_value() || split == H), "dlion ", what,
+              ": split must lie in [0, H], and be H without gamma_b");
+  for (const Tensor* g : {&gamma_a, gamma_b.has_value() ? &*gamma_b : &gamma_a})
+    TORCH_CHECK(g->is_cuda() && g->scalar_type() == at::kBFloat16 && g->is_contiguous() && g->numel() == D &&
+                    reinterpret_cast<uintptr_t>(g->data_ptr()) % 16 == 0,
+                "dlion ", what, ": gains must be contiguous, 16-byte aligned bf16 [D]");
+  TORCH_CHECK((cos == nullptr) == (sin == nullptr), "dlion ", what, ": cos/sin come as a pair");
+  if (cos != nullptr)
+    for (const Tensor* t : {cos, sin})
+      TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kBFloat16 && t->is_contiguous() && t->dim() == 2 &&
+                      t->size(0) >= T && t->size(1) == D,
+                  "dlion ", what, ": cos/sin must be contiguous bf16 [>=T, D]");
+}
+
+// (y [B, T, H, D] contiguous = rope(rms_norm(x) * gamma), rstd [B, T, H] fp32)
+std::tuple<Tensor, Tensor> qk_norm_rope_fwd(const Tensor& x, const Tensor& gamma_a,
+                                            const std::optional<Tensor>& gamma_b, int64_t split, double eps,
+                                            const Tensor& cos, const Tensor& sin) {
+  check_qk_norm("qk_norm_rope_fwd", x, gamma_a, gamma_b, split, &cos, &sin);
+  const int64_t B = x.size(0), T = x.size(1), H = x.size(2), D = x.size(3);
+  const c10::DeviceGuard dg(x.device());
+  auto y = at::empty(x.sizes(), x.options());
+  auto rstd = at::empty({B, T, H}, x.options().dtype(at::kFloat));
+  check_hip(dlion::launch_qk_norm_rope_fwd(x.data_ptr(), gamma_a.data_ptr(),
+                                           (gamma_b.has_value() ? *gamma_b : gamma_a).data_ptr(), cos.data_ptr(),
+                                           sin.data_ptr(), y.data_ptr(), rstd.data_ptr<float>(), B * T,
+                                           static_cast<int>(T), static_cast<int>(H), static_cast<int>(D),
+                                           static_cast<int>(split), static_cast<float>(eps), qk_token_stride(x), cur_stream()),
+            "qk_norm_rope_fwd");
+  return {y, rstd};
+}
+
+// in place: g (dz with cos / sin, dy = d loss / d (xh gamma) without) becomes dx; returns the fp32 gain-gradient
+// partials [parts, 2, D] (row 0: heads < split, row 1: the rest), part p over its own token rows
+Tensor qk_norm_rope_bwd_(const Tensor& g, const Tensor& x, const Tensor& rstd, const Tensor& gamma_a,
+                         const std::optional<Tensor>& gamma_b, int64_t split, const std::optional<Tensor>& cos,
+                         const std::optional<Tensor>& sin, int64_t parts) {
+  check_qk_norm("qk_norm_rope_bwd_", x, gamma_a, gamma_b, split, cos.has_value() ? &*cos : nullptr,
+                sin.has_value() ? &*sin : nullptr);
+  const int64_t B = x.size(0), T = x.size(1), H = x.size(2), D = x.size(3);
+  TORCH_CHECK(g.dim() == 4 && g.is_cuda() && g.scalar_type() == at::kBFloat16 && g.sizes() == x.sizes() &&
+                  qk_token_strided(g),
+              "dlion qk_norm_rope_bwd_: g must be bf16 of x's shape with contiguous heads and a uniform, 16-byte "
+              "aligned token stride");
+  TORCH_CHECK(rstd.is_cuda() && rstd.scalar_type() == at::kFloat && rstd.is_contiguous() && rstd.numel() == B * T * H,
+              "dlion qk_norm_rope_bwd_: rstd must be contiguous fp32 [B, T, H]");
+  TORCH_CHECK(parts >= 1 && parts <= (1 << 20), "dlion qk_norm_rope_bwd_: parts out of range");
+  const c10::DeviceGuard dg(x.device());
+  auto part = at::empty({parts, 2, D}, x.options().dtype(at::kFloat));
+  check_hip(dlion::launch_qk_norm_rope_bwd(g.data_ptr(), x.data_ptr(), rstd.data_ptr<float>(), gamma_a.data_ptr(),
+                                           (gamma_b.has_value() ? *gamma_b : gamma_a).data_ptr(),
+                                           cos.has_value() ? cos->data_ptr() : nullptr,
+                                           sin.has_value() ? sin->data_ptr() : nullptr, part.data_ptr<float>(),
+                                           static_cast<int>(parts), B * T, static_cast<int>(T), static_cast<int>(H),
+                                           static_cast<int>(D), static_cast<int>(split), qk_token_stride(g), qk_token_stride(x),
+                                           cur_stream()),
+            "qk_norm_rope_bwd_");
+  return part;
+}
+
 // ---------------------------------------------------------------- GEMM (NT)
 // a [M, K], b [N, K] (rows may be strided, unit column stride) -> c [M, N] bf16
 void check_gemm_operand(const Tensor& t, const char* name) {
@@ -1253,6 +1333,10 @@ TORCH_LIBRARY(dlion, m) {
   m.def("swiglu_fwd_t(Tensor g, Tensor u) -> (Tensor, Tensor)");
   m.def("rope(Tensor x, Tensor cos, Tensor sin, bool inverse) -> Tensor");
   m.def("rope_(Tensor(a!) x, Tensor cos, Tensor sin, bool inverse) -> ()");
+  m.def("qk_norm_rope_fwd(Tensor x, Tensor gamma_a, Tensor? gamma_b, int split, float eps, Tensor cos, Tensor sin)"
+        " -> (Tensor, Tensor)");
+  m.def("qk_norm_rope_bwd_(Tensor(a!) g, Tensor x, Tensor rstd, Tensor gamma_a, Tensor? gamma_b, int split,"
+        " Tensor? cos, Tensor? sin, int parts) -> Tensor");
   m.def(
       "add_norm_fwd(Tensor x, Tensor? y, Tensor? bias, Tensor gamma, Tensor? beta, float eps, bool rms, float p,"
       " int seed) -> (Tensor, Tensor, Tensor, Tensor)");
@@ -1320,6 +1404,8 @@ TORCH_LIBRARY_IMPL(dlion, CUDA, m) {
   m.impl("swiglu_fwd_t", &swiglu_fwd_t);
   m.impl("rope", &rope);
   m.impl("rope_", &rope_);
+  m.impl("qk_norm_rope_fwd", &qk_norm_rope_fwd);
+  m.impl("qk_norm_rope_bwd_", &qk_norm_rope_bwd_);
   m.impl("gemm_nt", &gemm_nt);
   m.impl("gemm_nt_out", &gemm_nt_out);
   m.impl("gemm_nt_gelu", &gemm_nt_gelu);

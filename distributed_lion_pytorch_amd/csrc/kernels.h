@@ -61,6 +61,16 @@ hipError_t launch_swiglu_bwd(const void* dh, const void* g, const void* u, void*
                              int64_t F, int64_t ld_in, int64_t ld_out, hipStream_t st);
 hipError_t launch_rope(const void* x, const void* cos, const void* sin, void* y, int64_t rows, int T, int H, int D,
                        bool inverse, int64_t x_ld, int64_t y_ld, hipStream_t st);
+// ---- per-head q/k RMSNorm + RoPE (qk_norm.hip); D in {64, 128}, heads [0, split) take gamma_a, the rest gamma_b
+// y [rows, Hx, D] contiguous, rstd [rows, Hx]; x token stride x_ld
+hipError_t launch_qk_norm_rope_fwd(const void* x, const void* gamma_a, const void* gamma_b, const void* cos,
+                                   const void* sin, void* y, float* rstd, int64_t rows, int T, int Hx, int D,
+                                   int split, float eps, int64_t x_ld, hipStream_t st);
+// in place on g (dz with cos / sin, dy with both null); part [parts, 2, D]: part p sums the token rows
+// [p rpp, min((p + 1) rpp, rows)), rpp = ceil(rows / parts)
+hipError_t launch_qk_norm_rope_bwd(void* g, const void* x, const float* rstd, const void* gamma_a, const void* gamma_b,
+                                   const void* cos, const void* sin, float* part, int parts, int64_t rows, int T,
+                                   int Hx, int D, int split, int64_t g_ld, int64_t x_ld, hipStream_t st);
 // out (+)= bf16(scale[0] * sum_s part[s]) (scale: optional device scalar)
 hipError_t launch_sum_partials(const float* part, int S, int64_t n, int64_t ld, void* out, bool accumulate,
                                hipStream_t st, const float* scale = nullptr);

@@ -16,7 +16,7 @@ from typing import Optional
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
-from transformers import LlamaConfig, MistralConfig, PreTrainedModel, Qwen2Config
+from transformers import LlamaConfig, MistralConfig, PreTrainedModel, Qwen2Config, Qwen3Config
 from transformers.modeling_outputs import CausalLMOutputWithPast
 
 from ..ops import fused
@@ -45,10 +45,27 @@ LLAMA_SIZES = {
     "qwen2-7b": dict(model_type="qwen2", hidden_size=3584, intermediate_size=18944, num_hidden_layers=28,
                      num_attention_heads=28, num_key_value_heads=4, vocab_size=152064, rope_theta=1000000.0,
                      max_position_embeddings=32768, rms_norm_eps=1e-6),
+    # Qwen3 (dense): head_dim 128 whatever the hidden size, per-head q/k RMSNorm, no projection biases
+    "qwen3-0.6b": dict(model_type="qwen3", hidden_size=1024, intermediate_size=3072, num_hidden_layers=28,
+                       num_attention_heads=16, num_key_value_heads=8, head_dim=128, vocab_size=151936,
+                       rope_theta=1000000.0, max_position_embeddings=40960, rms_norm_eps=1e-6,
+                       tie_word_embeddings=True),
+    "qwen3-1.7b": dict(model_type="qwen3", hidden_size=2048, intermediate_size=6144, num_hidden_layers=28,
+                       num_attention_heads=16, num_key_value_heads=8, head_dim=128, vocab_size=151936,
+                       rope_theta=1000000.0, max_position_embeddings=40960, rms_norm_eps=1e-6,
+                       tie_word_embeddings=True),
+    "qwen3-4b": dict(model_type="qwen3", hidden_size=2560, intermediate_size=9728, num_hidden_layers=36,
+                     num_attention_heads=32, num_key_value_heads=8, head_dim=128, vocab_size=151936,
+                     rope_theta=1000000.0, max_position_embeddings=40960, rms_norm_eps=1e-6,
+                     tie_word_embeddings=True),
+    "qwen3-8b": dict(model_type="qwen3", hidden_size=4096, intermediate_size=12288, num_hidden_layers=36,
+                     num_attention_heads=32, num_key_value_heads=8, head_dim=128, vocab_size=151936,
+                     rope_theta=1000000.0, max_position_embeddings=40960, rms_norm_eps=1e-6),
 }
 _ALIASES = {"Llama-2-7b-hf": "llama-2-7b", "Llama-2-7b": "llama-2-7b", "Meta-Llama-3-8B": "llama-3-8b",
             "Llama-3-8B": "llama-3-8b", "Llama-2-13b-hf": "llama-2-13b", "Mistral-7B-v0.1": "mistral-7b",
-            "Qwen2-0.5B": "qwen2-0.5b", "Qwen2-7B": "qwen2-7b"}
+            "Qwen2-0.5B": "qwen2-0.5b", "Qwen2-7B": "qwen2-7b", "Qwen3-0.6B": "qwen3-0.6b", "Qwen3-1.7B": "qwen3-1.7b",
+            "Qwen3-4B": "qwen3-4b", "Qwen3-8B": "qwen3-8b"}
 
 
 def llama_config(name: str = "llama-2-7b", **overrides) -> LlamaConfig:
@@ -59,8 +76,8 @@ def llama_config(name: str = "llama-2-7b", **overrides) -> LlamaConfig:
     kw = dict(LLAMA_SIZES[key])
     kw.update(overrides)
     kw.setdefault("tie_word_embeddings", False)
-    cls = {"mistral": MistralConfig, "qwen2": Qwen2Config}.get(kw.pop("model_type", "llama"), LlamaConfig)
-    return cls(**kw)
+    classes = {"mistral": MistralConfig, "qwen2": Qwen2Config, "qwen3": Qwen3Config}
+    return classes.get(kw.pop("model_type", "llama"), LlamaConfig)(**kw)
 
 
 class RMSNorm(nn.Module):
@@ -134,7 +151,7 @@ def _layer_window(cfg, i: int) -> int:
     types = getattr(cfg, "layer_types", None)
     if types is not None:
         return int(w) if types[i] == "sliding_attention" else 0
-    if getattr(cfg, "model_type", "") == "qwen2" and not getattr(cfg, "use_sliding_window", False):
+    if getattr(cfg, "model_type", "") in ("qwen2", "qwen3") and not getattr(cfg, "use_sliding_window", False):
         return 0
     return int(w)
 
@@ -152,6 +169,10 @@ class LlamaAttention(nn.Module):
         self.v_proj = nn.Linear(cfg.hidden_size, self.n_kv * self.head_dim, bias=qkv_bias)
         self.o_proj = nn.Linear(self.n_head * self.head_dim, cfg.hidden_size, bias=o_bias)
         self.attn_dropout = float(getattr(cfg, "attention_dropout", 0.0) or 0.0)
+        if getattr(cfg, "model_type", "") == "qwen3":
+            # Qwen3: RMSNorm over head_dim on every q and k head, between the projection and the rotation
+            self.q_norm = RMSNorm(self.head_dim, cfg.rms_norm_eps)
+            self.k_norm = RMSNorm(self.head_dim, cfg.rms_norm_eps)
 
     def forward(self, x, cos, sin, bounds=None):
         B, T, _ = x.shape
@@ -159,8 +180,12 @@ class LlamaAttention(nn.Module):
         q = q.view(B, T, self.n_head, self.head_dim)
         k = k.view(B, T, self.n_kv, self.head_dim)
         v = v.view(B, T, self.n_kv, self.head_dim)
-        y = fused.rope_attention(q, k, v, cos, sin, self.attn_dropout if self.training else 0.0, self.window,
-                                 bounds)
+        p = self.attn_dropout if self.training else 0.0
+        if hasattr(self, "q_norm"):
+            y = fused.rope_attention(q, k, v, cos, sin, p, self.window, bounds, self.q_norm.weight,
+                                     self.k_norm.weight, self.q_norm.eps)
+        else:
+            y = fused.rope_attention(q, k, v, cos, sin, p, self.window, bounds)
         return _lin(self.o_proj, y)
 
 
@@ -350,7 +375,9 @@ class LlamaForCausalLM(PreTrainedModel):
     def flops_per_token(self, seq_len: int) -> float:
         c = self.config
         n = self.num_parameters() - (0 if c.tie_word_embeddings else 0)
-        return 6 * n + 12 * c.num_hidden_layers * c.hidden_size * seq_len
+        # attention width: heads x head_dim (Qwen3's head_dim is independent of hidden_size)
+        width = c.num_attention_heads * (getattr(c, "head_dim", None) or c.hidden_size // c.num_attention_heads)
+        return 6 * n + 12 * c.num_hidden_layers * width * seq_len
 
 
 class MistralForCausalLM(LlamaForCausalLM):
@@ -369,6 +396,24 @@ class Qwen2ForCausalLM(LlamaForCausalLM):
     ``max_window_layers`` on; HF's Qwen2 parameter names."""
 
     config_class = Qwen2Config
+
+
+class Qwen3ForCausalLM(LlamaForCausalLM):
+    """Qwen3 (dense): the Llama architecture with an RMSNorm over head_dim on
+    every q and k head (``self_attn.q_norm`` / ``k_norm``, HF's names) between
+    the projection and the rotary embedding -- one fused kernel each way with
+    the rotation (csrc/qk_norm.hip) --, a head_dim independent of hidden_size,
+    biases by ``attention_bias`` and tied embeddings for the small sizes."""
+
+    config_class = Qwen3Config
+
+    def __init__(self, config: Qwen3Config):
+        rp = getattr(config, "rope_parameters", None)
+        kind = (rp.get("rope_type") or rp.get("type") or "default") if isinstance(rp, dict) else "default"
+        if kind != "default":
+            # Rotary builds plain tables only: wrong frequencies without a word would be worse than an error
+            raise NotImplementedError(f"native Qwen3: rope_type {kind!r} is not implemented (only 'default')")
+        super().__init__(config)
 
 
 def sequence_logps(model, input_ids: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:

@@ -100,6 +100,61 @@ def rope(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor) -> torch.Tensor:
     return rope_reference(x, cos, sin)
 
 
+# ------------------------------------------- per-head q/k RMSNorm + rotary (Qwen3)
+def qk_norm_rope_reference(x: torch.Tensor, gamma: torch.Tensor, eps: float, cos: torch.Tensor,
+                           sin: torch.Tensor) -> torch.Tensor:
+    """rope(RMSNorm_head_dim(x) * gamma) for x [B, T, H, D], gamma [D]: the
+    operation order of HF's Qwen3RMSNorm (normalise in fp32 -- fp64 stays fp64
+    --, cast back, then scale) followed by rope_reference."""
+    xf = x if x.dtype == torch.float64 else x.float()
+    y = xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps)
+    return rope_reference(gamma * y.to(x.dtype), cos, sin)
+
+
+def _qk_norm_parts(rows: int) -> int:
+    # a part is one 16-lane head-row group of csrc/qk_norm.hip over its own token rows: two
+    # tokens each keeps the fp32 partial stack [parts, 2, D] at a few percent of the row traffic
+    return max(1, min(8192, rows // 2))
+
+
+def _qk_norm_ok(x: torch.Tensor, *gammas) -> bool:
+    return (x.dtype == torch.bfloat16 and x.shape[-1] in (64, 128)
+            and all(g.dtype == torch.bfloat16 and g.is_contiguous() and g.data_ptr() % 16 == 0 for g in gammas)
+            and _use_hip(x))
+
+
+class _QKNormRope(torch.autograd.Function):
+    """rope(rms_norm(x) * gamma) over head rows: one gfx950 kernel each way
+    (csrc/qk_norm.hip); the gain gradient leaves the backward as fp32 partials."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, eps, cos, sin):
+        y, rstd = hip.ops().qk_norm_rope_fwd(x, gamma, None, x.shape[2], eps, cos, sin)
+        ctx.save_for_backward(x, rstd, gamma, cos, sin)
+        ctx.fused_params = _fused_params(gamma, None, None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dz):
+        x, rstd, gamma, cos, sin = ctx.saved_tensors
+        B, T, H, D = x.shape
+        g = dz.clone(memory_format=torch.contiguous_format)  # the kernel works in place
+        part = hip.ops().qk_norm_rope_bwd_(g, x, rstd, gamma, None, H, cos, sin, _qk_norm_parts(B * T))
+        dgamma, _, _ = _param_grads(part.view(-1, 2 * D), D, ctx.fused_params, (ctx.needs_input_grad[1], False, False))
+        return g, dgamma, None, None, None
+
+
+def qk_norm_rope(x: torch.Tensor, gamma: torch.Tensor, eps: float, cos: torch.Tensor,
+                 sin: torch.Tensor) -> torch.Tensor:
+    """x [B, T, H, D], gamma [D], cos/sin [>=T, D] -> rope(rms_norm(x) * gamma)."""
+    if cos.dtype == sin.dtype == torch.bfloat16 and _qk_norm_ok(x, gamma):
+        if not _token_strided_ok(x):
+            x = x.contiguous()
+        with torch.autocast("cuda", enabled=False):
+            return _QKNormRope.apply(x, gamma, float(eps), cos.contiguous(), sin.contiguous())
+    return qk_norm_rope_reference(x, gamma, eps, cos, sin)
+
+
 class _SwiGLU(torch.autograd.Function):
     """gate / up may be the two column halves of one fused projection output
     (row stride 2F): read in place, and the backward then writes [dgate | dup]
@@ -997,23 +1052,96 @@ class _RopeAttention(torch.autograd.Function):
 _ROPE_BWD_FUSED = True  # inverse rotation in the bwd kernels' stores (tests compare the separate pass)
 
 
+class _QKNormRopeAttention(torch.autograd.Function):
+    """_RopeAttention with Qwen3's per-head RMSNorm of q and k in front of the
+    rotation: csrc/qk_norm.hip's forward where ops.rope ran (one launch for the
+    adjacent q | k blocks), and after the attention backward its backward, in
+    place on the dq | dk columns of the packed gradient buffer.  Kept for the
+    backward: the pre-norm q | k view and rstd.  The gain gradients take the
+    RMSNorm gains' path (_param_grads)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, q_gamma, k_gamma, eps, cos, sin, p, seed, window=0, bounds=None):
+        ops = hip.ops()
+        H, Hkv = q.shape[2], k.shape[2]
+        qk = _adjacent_heads(q, k)
+        if qk is not None:
+            r, rstd_q = ops.qk_norm_rope_fwd(qk, q_gamma, k_gamma, H, eps, cos, sin)
+            qr, kr, rstd_k = r[:, :, :H], r[:, :, H:], None
+        else:
+            qr, rstd_q = ops.qk_norm_rope_fwd(q, q_gamma, None, H, eps, cos, sin)
+            kr, rstd_k = ops.qk_norm_rope_fwd(k, k_gamma, None, Hkv, eps, cos, sin)
+        row_lo, key_hi = bounds if bounds is not None else (None, None)
+        out, lse = ops.attn_fwd(qr, kr, v, p, seed, window, row_lo, key_hi)
+        ctx.save_for_backward(q, k, rstd_q, rstd_k, q_gamma, k_gamma, qr, kr, v, out, lse, cos, sin, row_lo, key_hi)
+        ctx.p, ctx.seed, ctx.window = p, seed, window
+        ctx.fused_params = _fused_params(q_gamma, k_gamma, None)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, rstd_q, rstd_k, q_gamma, k_gamma, qr, kr, v, out, lse, cos, sin, row_lo, key_hi = ctx.saved_tensors
+        B, T, H, D = qr.shape
+        Hkv = kr.shape[2]
+        buf = torch.empty(B, T, H + 2 * Hkv, D, dtype=qr.dtype, device=qr.device)
+        dq, dk, dv = buf[:, :, :H], buf[:, :, H:H + Hkv], buf[:, :, H + Hkv:]
+        ops = hip.ops()
+        if _ROPE_BWD_FUSED and cos.shape[-1] == D:
+            # the attention kernels store dq / dk through the inverse rotation: the norm backward sees dy
+            ops.attn_bwd(qr, kr, v, out, dout.contiguous(), lse, ctx.p, ctx.seed, dq, dk, dv, None,
+                         cos.reshape(-1, D), sin.reshape(-1, D), ctx.window, row_lo, key_hi)
+            c = s = None
+        else:
+            ops.attn_bwd(qr, kr, v, out, dout.contiguous(), lse, ctx.p, ctx.seed, dq, dk, dv, None, None, None,
+                         ctx.window, row_lo, key_hi)
+            c, s = cos, sin  # the norm backward rotates back first
+        need = ctx.needs_input_grad
+        parts = _qk_norm_parts(B * T)
+        qk = _adjacent_heads(q, k)
+        if qk is not None:
+            part = ops.qk_norm_rope_bwd_(buf[:, :, :H + Hkv], qk, rstd_q, q_gamma, k_gamma, H, c, s, parts)
+            dqg, dkg, _ = _param_grads(part.view(-1, 2 * D), D, ctx.fused_params, (need[3], need[4], False))
+        else:
+            fq, fk, _ = ctx.fused_params
+            part = ops.qk_norm_rope_bwd_(dq, q, rstd_q, q_gamma, None, H, c, s, parts)
+            dqg, _, _ = _param_grads(part.view(-1, 2 * D), D, (fq, None, None), (need[3], False, False))
+            part = ops.qk_norm_rope_bwd_(dk, k, rstd_k, k_gamma, None, Hkv, c, s, parts)
+            dkg, _, _ = _param_grads(part.view(-1, 2 * D), D, (fk, None, None), (need[4], False, False))
+        return dq, dk, dv, dqg, dkg, None, None, None, None, None, None, None
+
+
 def rope_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
-                   dropout_p: float = 0.0, window: int = 0, bounds=None) -> torch.Tensor:
+                   dropout_p: float = 0.0, window: int = 0, bounds=None, q_gamma=None, k_gamma=None,
+                   eps: float = 1e-6) -> torch.Tensor:
     """causal_attention_gqa(rope(q), rope(k), v, window, bounds) -> [B, T, H*D]; q [B,T,H,D],
-    k / v [B,T,Hkv,D] (views of a fused projection output are read in place)."""
+    k / v [B,T,Hkv,D] (views of a fused projection output are read in place).  With ``q_gamma`` /
+    ``k_gamma`` [D] (Qwen3) q and k are RMS-normalised over head_dim (``eps``) and scaled by them
+    before the rotation."""
     B, T, H, D = q.shape
     bounds = _check_bounds(bounds, B, T)
     window = 0 if bounds is not None else _eff_window(window, T)
+    if (q_gamma is None) != (k_gamma is None):
+        raise ValueError("rope_attention: q_gamma and k_gamma come as a pair")
     if q.is_cuda:
         from .linear import autocast_inputs
 
         q, k, v = autocast_inputs(q, k, v)
+        if q_gamma is not None:
+            q_gamma, k_gamma = autocast_inputs(q_gamma, k_gamma)
     if (_attn_ok(q, T, D, window, bounds, dropout_p) and cos.dtype == sin.dtype == torch.bfloat16
-            and k.dtype == v.dtype == torch.bfloat16 and all(_token_strided_ok(t) for t in (q, k, v))):
+            and k.dtype == v.dtype == torch.bfloat16 and all(_token_strided_ok(t) for t in (q, k, v))
+            and (q_gamma is None or _qk_norm_ok(q, q_gamma, k_gamma))):
         with torch.autocast("cuda", enabled=False):
-            out = _RopeAttention.apply(q, k, v, cos.contiguous(), sin.contiguous(), float(dropout_p), _new_seed(),
-                                       window, bounds)
+            if q_gamma is None:
+                out = _RopeAttention.apply(q, k, v, cos.contiguous(), sin.contiguous(), float(dropout_p),
+                                           _new_seed(), window, bounds)
+            else:
+                out = _QKNormRopeAttention.apply(q, k, v, q_gamma, k_gamma, float(eps), cos.contiguous(),
+                                                 sin.contiguous(), float(dropout_p), _new_seed(), window, bounds)
         return out.view(B, T, H * D)
+    if q_gamma is not None:
+        return causal_attention_gqa(qk_norm_rope(q, q_gamma, eps, cos, sin), qk_norm_rope(k, k_gamma, eps, cos, sin),
+                                    v, dropout_p, window, bounds)
     return causal_attention_gqa(rope(q, cos, sin), rope(k, cos, sin), v, dropout_p, window, bounds)
 
 

@@ -25,14 +25,22 @@ def activation_bytes(config, tokens: int, dtype_bytes: int = 2) -> int:
     summed over layers, for ``tokens`` tokens of one micro-batch: norm
     outputs, q/k/v, attention output, residual, MLP up/gate/activation and
     the activation's token-contiguous copy the down projection's weight
-    gradient may keep (ops/linear.py want_transposed_copy) -- ~6 x hidden + 4 x
-    intermediate elements per token per layer -- plus the LM-head logits of
-    the loss (fp32 worst case)."""
+    gradient may keep (ops/linear.py want_transposed_copy) -- ~3 x hidden
+    (norm outputs, residual) + 3 x attention width (q, k | v, attention output;
+    heads x head_dim, = hidden for every family but Qwen3) + 4 x intermediate
+    elements per token per layer -- plus the LM-head logits of the loss (fp32
+    worst case).  Qwen3 also keeps the pre-norm q | k block and its fp32 rstd
+    (csrc/qk_norm.hip)."""
     h = getattr(config, "hidden_size", None) or getattr(config, "n_embd")
     ff = getattr(config, "intermediate_size", None) or getattr(config, "n_inner", None) or 4 * h
     layers = getattr(config, "num_hidden_layers", None) or getattr(config, "n_layer")
     vocab = getattr(config, "vocab_size", 0)
-    per_layer = (6 * h + 4 * ff) * dtype_bytes
+    heads = getattr(config, "num_attention_heads", None) or getattr(config, "n_head")
+    hd = getattr(config, "head_dim", None) or h // heads
+    per_layer = (3 * h + 3 * heads * hd + 4 * ff) * dtype_bytes
+    if getattr(config, "model_type", "") == "qwen3":
+        qk_heads = heads + (getattr(config, "num_key_value_heads", None) or heads)
+        per_layer += qk_heads * hd * dtype_bytes + qk_heads * 4
     return tokens * (layers * per_layer + 4 * vocab)
 
 

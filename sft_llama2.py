@@ -186,7 +186,7 @@ def main(argv=None):
 
         if not isinstance(model, LlamaForCausalLM):
             # another model would drop or misread the position_ids and train with cross-sample attention
-            raise ValueError(f"--isolate_documents needs a native Llama-family model (llama, mistral, qwen2); "
+            raise ValueError(f"--isolate_documents needs a native Llama-family model (llama, mistral, qwen2, qwen3); "
                              f"{type(model).__module__}.{type(model).__name__} (model_type "
                              f"{model.config.model_type!r}) does not isolate packed samples")
     if script_args.load_in_4bit:
