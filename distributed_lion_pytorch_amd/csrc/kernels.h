@@ -123,7 +123,7 @@ hipError_t launch_gemm_tn(const void* const* P, const void* const* Q, int nseg, 
 hipError_t launch_gemm_nt_stamped(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K,
                                   unsigned long long* stamps, hipStream_t st);
 
-// ---- LoRA adapter streams (lora.hip), bf16, r in {8, 16}, widths % 8 == 0
+// ---- LoRA adapter streams (lora.hip), bf16, r in {8, 16} (wide ranks below), widths % 8 == 0
 // out[t, :r] = scale * drop(in)[t, :] . w^T, w [r, K]; dropout when thresh16 > 0
 hipError_t launch_lora_rows(const void* in, int64_t ldin, const void* w, void* out, int64_t rows, int K, int r,
                             float scale, uint32_t seed, uint32_t thresh16, float inv_keep, hipStream_t st);
@@ -137,6 +137,18 @@ int lora_cols_parts(int64_t rows, int N);
 hipError_t launch_lora_cols(const void* g, int64_t ldg, const void* y, const void* a, void* dx, float* part, int64_t rows,
                             int N, int r, int parts, int mode, float yscale, uint32_t seed, uint32_t thresh16,
                             float inv_keep, hipStream_t st);
+// the same three streams for r in {32, 64, 128} (lora_wide.hip): MFMA forms of all three.  lora_cols_parts_wide
+// picks the range count: min(ceil(1024 / ceil(N / 128)), rows / (2 r)) but at least 1, so that the fp32 partials
+// never exceed the bytes of the g operand
+bool lora_wide_rank(int r);
+hipError_t launch_lora_rows_wide(const void* in, int64_t ldin, const void* w, void* out, int64_t rows, int K, int r,
+                                 float scale, uint32_t seed, uint32_t thresh16, float inv_keep, hipStream_t st);
+hipError_t launch_lora_up_wide(const void* o, int64_t ldo, const void* u, const void* b, void* out, int64_t rows, int N,
+                               int r, float s, hipStream_t st);
+int lora_cols_parts_wide(int64_t rows, int N, int r);
+hipError_t launch_lora_cols_wide(const void* g, int64_t ldg, const void* y, const void* a, void* dx, float* part,
+                                 int64_t rows, int N, int r, int parts, int mode, float yscale, uint32_t seed,
+                                 uint32_t thresh16, float inv_keep, hipStream_t st);
 
 // ---- 4-bit blockwise quantization of frozen weights (quant.hip); n % 64 == 0, 16-byte aligned
 // q [n / 2] uint8 (first element of a pair in the high nibble), absmax [n / 64] fp32, code [16] fp32

@@ -71,8 +71,10 @@ class LoraLinear(nn.Module):
         return self.lora_B(self.lora_A(self.dropout(x))) * self.scaling
 
     def add_adapter(self, x, y):
-        """y + lora_delta(x); on the GPU the fused csrc/lora.hip kernels
-        (ops/fused.lora_add), with the dropout mask drawn in-kernel."""
+        """y + lora_delta(x); on the GPU the fused kernels of csrc/lora.hip
+        (r = 8, 16) and csrc/lora_wide.hip (r = 32, 64, 128) through
+        ops/fused.lora_add, with the dropout mask drawn in-kernel.  Any other
+        rank runs the unfused ATen chain."""
         if self.merged:
             return y
         p = self.dropout.p if isinstance(self.dropout, nn.Dropout) and self.dropout.training else 0.0

@@ -1162,7 +1162,8 @@ def _lora_weight_grad(param, part2d: torch.Tensor, fuse: bool):
 
 
 class _LoraAdd(torch.autograd.Function):
-    """out = o + s * (drop(x) A^T) B^T with the csrc/lora.hip streams: the
+    """out = o + s * (drop(x) A^T) B^T with the csrc/lora.hip streams (r = 8,
+    16; csrc/lora_wide.hip behind the same three ops at r = 32, 64, 128): the
     forward reads x once (dropout from the stateless hash, never stored) and
     o once; the backward reads dout twice (du, dB) and x once (dA and dx in
     the same pass).  o's gradient is dout itself, so a fused projection's
@@ -1200,14 +1201,36 @@ class _LoraAdd(torch.autograd.Function):
 
 
 _LORA_FUSED = True  # fused LoRA kernels (tests compare the unfused chain)
+# ranks with fused kernels: 8 / 16 keep the rank in registers (csrc/lora.hip),
+# 32 / 64 / 128 run it on the matrix cores (csrc/lora_wide.hip)
+LORA_FUSED_RANKS = (8, 16, 32, 64, 128)
+
+
+def lora_cols_parts(rows: int, N: int, r: int):
+    """(P, rpp, ranges) of lora_cols' fp32 partials, as the launchers pick them.
+    r in {8, 16}: P = min(512 // ceil(N / 512), ceil(rows / 16)).  r in {32, 64,
+    128}: P = min(ceil(1024 / ceil(N / 128)), rows // (2 r)), so that the
+    partials ([P, N, r] fp32) never exceed the bytes of the g operand ([rows, N]
+    bf16) while ~1024 blocks of 128 columns still fill the chip.  P is at least
+    1 either way; rpp = ceil(rows / P) and part p sums the rows [p rpp,
+    min((p + 1) rpp, rows)) -- an empty range (a part of +0) where p rpp >= rows."""
+    if r in (8, 16):
+        P = min(512 // ((N + 511) // 512), (rows + 15) // 16)
+    else:
+        cblocks = (N + 127) // 128
+        P = min((1024 + cblocks - 1) // cblocks, rows // (2 * r))
+    P = max(1, P)
+    rpp = (rows + P - 1) // P
+    return P, rpp, [(min(p * rpp, rows), min((p + 1) * rpp, rows)) for p in range(P)]
 
 
 def lora_add(o: torch.Tensor, x: torch.Tensor, a: torch.Tensor, b: torch.Tensor, scaling: float,
              p: float) -> torch.Tensor:
     """o + dropout(x, p) A^T B^T * scaling (peft's LoRA output, A [r, K],
-    B [N, r]); the fused HIP path for bf16 GPU tensors with r in {8, 16}."""
+    B [N, r]); the fused HIP path for bf16 GPU tensors with r in
+    LORA_FUSED_RANKS, the ATen chain for every other rank."""
     r = a.shape[0]
-    if _LORA_FUSED and x.is_cuda and r in (8, 16) and _use_hip(x):
+    if _LORA_FUSED and x.is_cuda and r in LORA_FUSED_RANKS and _use_hip(x):
         from .linear import autocast_inputs
 
         o_, x_, a_, b_ = autocast_inputs(o, x, a, b)
