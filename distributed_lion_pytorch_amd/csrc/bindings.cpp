@@ -238,6 +238,26 @@ Tensor softmax_xent_(const Tensor& logits, const Tensor& labels, int64_t v, int6
   return loss;
 }
 
+// label smoothing + z-loss form: logits <- (1 + 2 z lse) softmax - (1 - smoothing) onehot - smoothing / v
+Tensor softmax_xent_opts_(const Tensor& logits, const Tensor& labels, int64_t v, double smoothing, double z_loss,
+                          int64_t variant) {
+  check_dev(logits, "logits");
+  check_dev(labels, "labels");
+  TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous(), "dlion: logits must be a contiguous [N, Vpad]");
+  TORCH_CHECK(labels.scalar_type() == at::kLong && labels.numel() == logits.size(0) && labels.is_contiguous(),
+              "dlion: labels must be int64[N]");
+  TORCH_CHECK(logits.size(1) % 8 == 0 && v > 0 && v <= logits.size(1), "dlion: padded vocab must be a multiple of 8");
+  TORCH_CHECK(smoothing >= 0.0 && smoothing < 1.0 && z_loss >= 0.0, "dlion: need 0 <= smoothing < 1 and z_loss >= 0");
+  const c10::DeviceGuard g(logits.device());
+  auto loss = at::empty({logits.size(0)}, logits.options().dtype(at::kFloat));
+  check_hip(dlion::launch_softmax_xent_opts(dtype_code(logits.scalar_type()), logits.data_ptr(),
+                                            labels.data_ptr<int64_t>(), logits.size(0), logits.size(1),
+                                            static_cast<int>(v), loss.data_ptr<float>(), static_cast<float>(smoothing),
+                                            static_cast<float>(z_loss), static_cast<int>(variant), cur_stream()),
+            "softmax_xent_opts");
+  return loss;
+}
+
 // ------------------------------------------------------------ flash attention
 void check_bthd(const Tensor& t, const char* name) {
   TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16, "dlion attn: ", name, " must be a bf16 GPU tensor");
@@ -1363,6 +1383,7 @@ TORCH_LIBRARY(dlion, m) {
       " Tensor(a!) dq, Tensor(b!) dk, Tensor(c!) dv, Tensor(d!)? colsum=None, Tensor? rope_cos=None,"
       " Tensor? rope_sin=None, int window=0, Tensor? row_lo=None, Tensor? key_hi=None) -> ()");
   m.def("softmax_xent_(Tensor(a!) logits, Tensor labels, int v, int variant=0) -> Tensor");
+  m.def("softmax_xent_opts_(Tensor(a!) logits, Tensor labels, int v, float smoothing, float z_loss, int variant=0) -> Tensor");
   m.def(
       "lion_local(Tensor meta, int seg_off, int chunk_off, int n_chunks, int dtype, float decay, float neg_lr,"
       " float b1, float omb1, float b2, float omb2, Tensor? gscale=None, int rounding=0, int rkey=0,"
@@ -1392,6 +1413,7 @@ TORCH_LIBRARY_IMPL(dlion, CUDA, m) {
   m.impl("grad_sumsq", &grad_sumsq);
   m.impl("clip_coef", &clip_coef);
   m.impl("softmax_xent_", &softmax_xent_);
+  m.impl("softmax_xent_opts_", &softmax_xent_opts_);
   m.impl("attn_fwd", &attn_fwd);
   m.impl("attn_bwd", &attn_bwd);
   m.impl("add_norm_fwd", &add_norm_fwd);

@@ -164,5 +164,9 @@ hipError_t launch_dequant4_t(int dt, const uint8_t* q, const float* absmax, cons
 // variant 0 = auto (DLION_XENT env override), 1 fp32-row, 2 streaming, 3/4/5 packed 16-bit row (256/512/1024 thr)
 hipError_t launch_softmax_xent(int dt, void* logits, const int64_t* labels, int64_t n, int64_t vp, int v, float* loss,
                                int variant, hipStream_t st);
+// label smoothing eps in [0, 1) and z-loss weight zeta >= 0 (kernels of their own, same variants):
+// loss = lse - (1 - eps) x_y - eps mean(x) + zeta lse^2, logits <- (1 + 2 zeta lse) p - (1 - eps) onehot - eps / v
+hipError_t launch_softmax_xent_opts(int dt, void* logits, const int64_t* labels, int64_t n, int64_t vp, int v,
+                                    float* loss, float eps, float zeta, int variant, hipStream_t st);
 
 }  // namespace dlion

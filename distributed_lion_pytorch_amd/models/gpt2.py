@@ -29,6 +29,7 @@ from transformers.modeling_outputs import CausalLMOutputWithCrossAttentions
 
 from ..ops import fused
 from ..ops.linear import linear_kn, no_wgrad_deferral_this_window
+from .loss_options import LossOptionsMixin
 
 GPT2_SIZES = {
     "gpt2": dict(n_embd=768, n_layer=12, n_head=12),
@@ -151,7 +152,7 @@ class GPT2Model(nn.Module):
         return h
 
 
-class GPT2LMHeadModel(PreTrainedModel):
+class GPT2LMHeadModel(LossOptionsMixin, PreTrainedModel):
     config_class = GPT2Config
     base_model_prefix = "transformer"
     _tied_weights_keys = {"lm_head.weight": "transformer.wte.weight"}
@@ -217,7 +218,8 @@ class GPT2LMHeadModel(PreTrainedModel):
             # shift inside the fused LM-head + cross-entropy (HF semantics:
             # position t predicts label t+1, ignore_index -100).  With
             # num_items_in_batch the sum is normalised by it (HF GA-aware loss).
-            loss = fused.causal_lm_loss(h, self.lm_head.weight, labels, normalizer=num_items_in_batch)
+            loss = fused.causal_lm_loss(h, self.lm_head.weight, labels, normalizer=num_items_in_batch,
+                                        **self._loss_options())
             if not self.training:
                 logits = F.linear(h, self.lm_head.weight)
         else:

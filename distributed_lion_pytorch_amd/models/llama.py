@@ -21,6 +21,7 @@ from transformers.modeling_outputs import CausalLMOutputWithPast
 
 from ..ops import fused
 from ..ops.linear import linear_multi_nk, linear_nk, no_wgrad_deferral_this_window
+from .loss_options import LossOptionsMixin
 
 LLAMA_SIZES = {
     "llama-2-7b": dict(hidden_size=4096, intermediate_size=11008, num_hidden_layers=32, num_attention_heads=32,
@@ -305,7 +306,7 @@ class LlamaModel(nn.Module):
         return h
 
 
-class LlamaForCausalLM(PreTrainedModel):
+class LlamaForCausalLM(LossOptionsMixin, PreTrainedModel):
     config_class = LlamaConfig
     base_model_prefix = "model"
     _tied_weights_keys = {"lm_head.weight": "model.embed_tokens.weight"}
@@ -361,7 +362,8 @@ class LlamaForCausalLM(PreTrainedModel):
         h = self.model(input_ids, position_ids)
         loss = logits = None
         if labels is not None:
-            loss = fused.causal_lm_loss(h, self.lm_head.weight, labels, normalizer=num_items_in_batch)
+            loss = fused.causal_lm_loss(h, self.lm_head.weight, labels, normalizer=num_items_in_batch,
+                                        **self._loss_options())
             if not self.training:
                 logits = F.linear(h, self.lm_head.weight)
         else:

@@ -1378,10 +1378,15 @@ class _LMHeadCE(torch.autograd.Function):
     the forward pass (the loss gradient is a scalar multiple of
     softmax - onehot), so the [N, V] logits never persist and never exist in
     fp32.  The vocabulary is padded to a multiple of 64 for aligned rows and
-    well-shaped GEMMs; padded columns are masked out of the softmax."""
+    well-shaped GEMMs; padded columns are masked out of the softmax.
+
+    With ``label_smoothing`` (eps) or ``z_loss`` (zeta) the row loss is
+    lse - (1 - eps) x_y - eps mean(x) + zeta lse^2 and the stored matrix
+    (1 + 2 zeta lse) softmax - (1 - eps) onehot - eps / V: still one in-place
+    matrix scaled by a scalar in the backward, so every route below is the same."""
 
     @staticmethod
-    def forward(ctx, h2d, weight, labels1d, normalizer=None):
+    def forward(ctx, h2d, weight, labels1d, normalizer=None, label_smoothing: float = 0.0, z_loss: float = 0.0):
         v = weight.shape[0]
         need_grad = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
         wp = _pad_rows(weight)
@@ -1391,10 +1396,15 @@ class _LMHeadCE(torch.autograd.Function):
         else:
             n_valid = torch.as_tensor(normalizer, dtype=torch.float32, device=h2d.device).clamp_min(1)
         check_labels(labels1d, v)
-        if _use_hip(logits):
-            row_loss = hip.ops().softmax_xent_(logits, labels1d, v)  # logits <- softmax - onehot (in place)
+        if label_smoothing == 0.0 and z_loss == 0.0:  # the plain op, unchanged
+            if _use_hip(logits):
+                row_loss = hip.ops().softmax_xent_(logits, labels1d, v)  # logits <- softmax - onehot (in place)
+            else:
+                row_loss = _softmax_xent_torch_(logits, labels1d, v)
+        elif _use_hip(logits):
+            row_loss = hip.ops().softmax_xent_opts_(logits, labels1d, v, label_smoothing, z_loss)
         else:
-            row_loss = _softmax_xent_torch_(logits, labels1d, v)
+            row_loss = _softmax_xent_torch_(logits, labels1d, v, label_smoothing, z_loss)
         loss = row_loss.sum() / n_valid
         if need_grad:
             dh = _lm_dgrad(logits, weight, wp)  # [N, C]
@@ -1444,7 +1454,7 @@ class _LMHeadCE(torch.autograd.Function):
             scale = (g / n_valid).to(dh.dtype)
             gh = dh * scale if ctx.needs_input_grad[0] else None
             gw = dw * scale if ctx.has_dw and ctx.needs_input_grad[1] else None
-            return gh, gw, None, None
+            return gh, gw, None, None, None, None
         # one pass each: bf16(x * bf16(g / n)) with the scale on the device; the
         # weight gradient is added straight into .grad inside a fusion window
         # (tied GPT-2 wte: the embedding backward then adds its rows in place)
@@ -1477,7 +1487,7 @@ class _LMHeadCE(torch.autograd.Function):
                     w.grad = out if w.grad is None else w.grad + out
                 else:
                     gw = out
-        return gh, gw, None, None
+        return gh, gw, None, None, None, None
 
     @staticmethod
     def _backward_deferred(ctx, g):
@@ -1499,7 +1509,7 @@ class _LMHeadCE(torch.autograd.Function):
         if not linear._defer_wgrad([w], [(0, v * c)], logits, hs, split):
             part = ops.gemm_tn([logits], [hs], split)  # over budget / window closed: now
             linear.deposit_grad(w, part.view(split, -1)[:, : v * c], defer=False)
-        return gh, None, None, None
+        return gh, None, None, None, None, None
 
 
     @staticmethod
@@ -1526,7 +1536,7 @@ class _LMHeadCE(torch.autograd.Function):
                 w.grad = out if w.grad is None else w.grad + out
             else:
                 gw = out
-        return gh, gw, None, None
+        return gh, gw, None, None, None, None
 
 
 def _lm_late_ok(weight, logits, h2d, v) -> bool:
@@ -1557,14 +1567,28 @@ def _lm_defer_ok(weight, logits, h2d) -> bool:
 
 
 
-def _softmax_xent_torch_(logits: torch.Tensor, labels: torch.Tensor, v: int) -> torch.Tensor:
+def _softmax_xent_torch_(logits: torch.Tensor, labels: torch.Tensor, v: int, label_smoothing: float = 0.0,
+                         z_loss: float = 0.0) -> torch.Tensor:
     """In-place reference of the HIP kernel: logits[:, :v] <- softmax - onehot
-    (zero rows for ignored labels, zero padded columns); returns fp32 row loss."""
+    (zero rows for ignored labels, zero padded columns); returns fp32 row loss.
+    With options: (1 + 2 z lse) softmax - (1 - eps) onehot - eps / v and
+    lse - (1 - eps) x_y - eps mean(x) + z lse^2."""
     x = logits[:, :v].float()
     lse = torch.logsumexp(x, dim=1)
     valid = labels != -100
     safe = labels.clamp_min(0)
     tgt = x.gather(1, safe[:, None]).squeeze(1)
+    if label_smoothing != 0.0 or z_loss != 0.0:
+        eps, z = float(label_smoothing), float(z_loss)
+        row = lse - (1.0 - eps) * tgt - eps * x.mean(dim=1) + z * lse * lse
+        row_loss = torch.where(valid, row, torch.zeros_like(lse))
+        prob = torch.exp(x - lse[:, None]) * (1.0 + 2.0 * z * lse)[:, None] - eps / v
+        prob.scatter_add_(1, safe[:, None], torch.full_like(tgt, -(1.0 - eps))[:, None])
+        prob[~valid] = 0.0
+        logits[:, :v] = prob.to(logits.dtype)
+        if logits.shape[1] > v:
+            logits[:, v:] = 0
+        return row_loss
     row_loss = torch.where(valid, lse - tgt, torch.zeros_like(lse))
     prob = torch.exp(x - lse[:, None])
     prob.scatter_add_(1, safe[:, None], -torch.ones_like(tgt)[:, None])
@@ -1623,20 +1647,35 @@ def token_logps(h: torch.Tensor, weight: torch.Tensor, labels: torch.Tensor) -> 
     return _TokenLogp.apply(h2d.contiguous(), weight, lab).view(labels.shape)
 
 
+def check_loss_options(label_smoothing: float, z_loss: float):
+    """(label_smoothing, z_loss) as plain floats; ValueError unless
+    0 <= label_smoothing < 1 and z_loss >= 0."""
+    eps, z = float(label_smoothing), float(z_loss)
+    if not 0.0 <= eps < 1.0:
+        raise ValueError(f"label_smoothing must be in [0, 1), got {label_smoothing!r}")
+    if not z >= 0.0 or z == float("inf"):
+        raise ValueError(f"z_loss must be a finite value >= 0, got {z_loss!r}")
+    return eps, z
+
+
 def lm_head_cross_entropy(h: torch.Tensor, weight: torch.Tensor, labels: torch.Tensor,
-                          normalizer=None) -> torch.Tensor:
+                          normalizer=None, label_smoothing: float = 0.0, z_loss: float = 0.0) -> torch.Tensor:
     """Token cross-entropy of ``h @ weight.T`` against ``labels`` (-100 ignored):
-    mean over valid tokens, or sum / ``normalizer`` (HF ``num_items_in_batch``)."""
+    mean over valid tokens, or sum / ``normalizer`` (HF ``num_items_in_batch``).
+    ``label_smoothing`` (HF ``LabelSmoother`` / ``F.cross_entropy`` semantics:
+    the uniform term is the mean over the real vocabulary) and ``z_loss``
+    (``z_loss * logsumexp^2`` per token) are computed inside the fused kernel."""
+    eps, z = check_loss_options(label_smoothing, z_loss)
     h2d = h.reshape(-1, h.shape[-1])
     if h2d.is_cuda:
         from .linear import autocast_inputs
 
         h2d, weight = autocast_inputs(h2d, weight)
         with torch.autocast("cuda", enabled=False):
-            return _LMHeadCE.apply(h2d, weight, labels.reshape(-1), normalizer)
+            return _LMHeadCE.apply(h2d, weight, labels.reshape(-1), normalizer, eps, z)
     if h2d.dtype != weight.dtype:
         h2d = h2d.to(weight.dtype)
-    return _LMHeadCE.apply(h2d, weight, labels.reshape(-1), normalizer)
+    return _LMHeadCE.apply(h2d, weight, labels.reshape(-1), normalizer, eps, z)
 
 
 def shift_labels(labels: torch.Tensor) -> torch.Tensor:
@@ -1650,9 +1689,11 @@ def shift_labels(labels: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def causal_lm_loss(h: torch.Tensor, weight: torch.Tensor, labels: torch.Tensor, normalizer=None) -> torch.Tensor:
+def causal_lm_loss(h: torch.Tensor, weight: torch.Tensor, labels: torch.Tensor, normalizer=None,
+                   label_smoothing: float = 0.0, z_loss: float = 0.0) -> torch.Tensor:
     """Shifted next-token cross-entropy of the LM head on h [B, T, C]."""
-    return lm_head_cross_entropy(h, weight, shift_labels(labels), normalizer=normalizer)
+    return lm_head_cross_entropy(h, weight, shift_labels(labels), normalizer=normalizer,
+                                 label_smoothing=label_smoothing, z_loss=z_loss)
 
 
 def reference_lm_loss(h, weight, labels):

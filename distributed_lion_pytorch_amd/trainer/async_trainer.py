@@ -70,6 +70,9 @@ class LionArguments:
     lion_ddp_wrap: bool = field(default=False, metadata={
         "help": "async trainers: let accelerate wrap the model in DDP as the reference does (its gradient "
                 "buckets are never used under no_sync; default: no wrap, replicas initialised by one broadcast)"})
+    lm_z_loss: float = field(default=0.0, metadata={
+        "help": "auxiliary z-loss weight: adds lm_z_loss * logsumexp(logits)^2 per token to the training loss "
+                "inside the fused LM-head cross-entropy (native models only; 0 = off)"})
 
 
 def apply_lion_args(training_args, lion_args: LionArguments):
@@ -146,6 +149,31 @@ def build_lion(model: torch.nn.Module, args, lr: Optional[float] = None, weight_
     return opt
 
 
+def route_loss_options(trainer) -> None:
+    """``--label_smoothing_factor`` / ``--lm_z_loss`` on a native model: hand
+    them to the model's fused LM-head cross-entropy (``set_loss_options``) and
+    drop HF's ``LabelSmoother``.  With the smoother, ``Trainer.compute_loss``
+    pops the labels and the model has to return full fp32-bound [B, T, V]
+    logits; without it the labels and ``num_items_in_batch`` reach the model
+    as on a run without the flag.  A stock HF model keeps HF's smoother; a
+    non-zero z-loss needs a native model."""
+    args = trainer.args
+    model = getattr(trainer.model, "module", trainer.model)
+    native = callable(getattr(model, "set_loss_options", None))
+    z = float(getattr(args, "lm_z_loss", 0.0) or 0.0)
+    if z != 0.0 and not native:
+        raise ValueError("--lm_z_loss needs a native model (the z-loss is computed by the fused LM-head "
+                         f"cross-entropy); {type(model).__name__} has no set_loss_options")
+    if not native:
+        return
+    smoother = getattr(trainer, "label_smoother", None)
+    if smoother is not None:
+        model.set_loss_options(label_smoothing=float(args.label_smoothing_factor), z_loss=z)
+        trainer.label_smoother = None
+    elif z != 0.0:
+        model.set_loss_options(label_smoothing=model.label_smoothing, z_loss=z)
+
+
 def no_sync(model):
     """DDP.no_sync() when the model is DDP-wrapped, otherwise a no-op (D14)."""
     fn = getattr(model, "no_sync", None)
@@ -167,6 +195,10 @@ class AsyncMixin:
     last micro-batch), and gradient clipping uses Lion's fused norm (the clip
     coefficient stays on the device and is applied inside the update kernels)
     when Lion owns exactly the model's trainable parameters."""
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        route_loss_options(self)
 
     def _engine_fusion(self, model) -> bool:
         if os.environ.get("DLION_HF_FUSION", "1") == "0":
@@ -519,6 +551,10 @@ class RankShardedLoaderMixin:
     iterable data) or wrap it in an ``IterableDatasetShard`` that drops
     (W-1)/W of the already-sharded batches.  Batches are moved to the device by
     ``_prepare_inputs``."""
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        route_loss_options(self)
 
     def train(self, *a, **kw):
         _share_gpus_if_oversubscribed(self.args)

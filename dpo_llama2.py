@@ -171,6 +171,11 @@ def train_eval_pairs(args):
 def main(argv=None):
     parser = HfArgumentParser((ScriptArguments, LionArguments))
     script_args, lion_args = parser.parse_args_into_dataclasses(args=argv)
+    if lion_args.lm_z_loss != 0.0:
+        # the z-loss lives in the fused LM-head cross-entropy; DPO's loss is built from
+        # sequence log-probabilities and never runs it (its own label_smoothing is cDPO's)
+        raise SystemExit("dpo_llama2.py: --lm_z_loss is not supported for DPO (the z-loss belongs to the "
+                         "language-modelling cross-entropy of run_clm.py / sft_llama2.py)")
     logging.basicConfig(level=logging.INFO, handlers=[logging.StreamHandler(sys.stdout)])
     transformers.set_seed(script_args.seed)
 
