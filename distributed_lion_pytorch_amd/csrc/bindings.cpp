@@ -12,6 +12,7 @@
 
 #include <cstdlib>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "kernels.h"
@@ -256,6 +257,31 @@ Tensor softmax_xent_opts_(const Tensor& logits, const Tensor& labels, int64_t v,
                                             static_cast<float>(z_loss), static_cast<int>(variant), cur_stream()),
             "softmax_xent_opts");
   return loss;
+}
+
+// forward-only scoring of read-only logits: (row_loss, lse, pred, rank), see kernels.h
+std::tuple<Tensor, Tensor, Tensor, Tensor> lm_score(const Tensor& logits, const Tensor& labels, int64_t v,
+                                                    double smoothing, double z_loss) {
+  check_dev(logits, "logits");
+  check_dev(labels, "labels");
+  TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous(), "dlion: logits must be a contiguous [N, Vpad]");
+  TORCH_CHECK(labels.scalar_type() == at::kLong && labels.numel() == logits.size(0) && labels.is_contiguous(),
+              "dlion: labels must be int64[N]");
+  TORCH_CHECK(logits.size(1) % 8 == 0 && v > 0 && v <= logits.size(1), "dlion: padded vocab must be a multiple of 8");
+  TORCH_CHECK(logits.size(1) <= (int64_t{1} << 30), "dlion: lm_score vocabulary too wide");
+  TORCH_CHECK(smoothing >= 0.0 && smoothing < 1.0 && z_loss >= 0.0, "dlion: need 0 <= smoothing < 1 and z_loss >= 0");
+  const c10::DeviceGuard g(logits.device());
+  const int64_t n = logits.size(0);
+  auto loss = at::empty({n}, logits.options().dtype(at::kFloat));
+  auto lse = at::empty({n}, logits.options().dtype(at::kFloat));
+  auto pred = at::empty({n}, logits.options().dtype(at::kInt));
+  auto rank = at::empty({n}, logits.options().dtype(at::kInt));
+  check_hip(dlion::launch_lm_score(dtype_code(logits.scalar_type()), logits.data_ptr(), labels.data_ptr<int64_t>(), n,
+                                   logits.size(1), static_cast<int>(v), static_cast<float>(smoothing),
+                                   static_cast<float>(z_loss), loss.data_ptr<float>(), lse.data_ptr<float>(),
+                                   pred.data_ptr<int>(), rank.data_ptr<int>(), cur_stream()),
+            "lm_score");
+  return {loss, lse, pred, rank};
 }
 
 // ------------------------------------------------------------ flash attention
@@ -1384,6 +1410,7 @@ TORCH_LIBRARY(dlion, m) {
       " Tensor? rope_sin=None, int window=0, Tensor? row_lo=None, Tensor? key_hi=None) -> ()");
   m.def("softmax_xent_(Tensor(a!) logits, Tensor labels, int v, int variant=0) -> Tensor");
   m.def("softmax_xent_opts_(Tensor(a!) logits, Tensor labels, int v, float smoothing, float z_loss, int variant=0) -> Tensor");
+  m.def("lm_score(Tensor logits, Tensor labels, int v, float smoothing, float z_loss) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def(
       "lion_local(Tensor meta, int seg_off, int chunk_off, int n_chunks, int dtype, float decay, float neg_lr,"
       " float b1, float omb1, float b2, float omb2, Tensor? gscale=None, int rounding=0, int rkey=0,"
@@ -1414,6 +1441,7 @@ TORCH_LIBRARY_IMPL(dlion, CUDA, m) {
   m.impl("clip_coef", &clip_coef);
   m.impl("softmax_xent_", &softmax_xent_);
   m.impl("softmax_xent_opts_", &softmax_xent_opts_);
+  m.impl("lm_score", &lm_score);
   m.impl("attn_fwd", &attn_fwd);
   m.impl("attn_bwd", &attn_bwd);
   m.impl("add_norm_fwd", &add_norm_fwd);

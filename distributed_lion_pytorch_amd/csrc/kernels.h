@@ -169,4 +169,10 @@ hipError_t launch_softmax_xent(int dt, void* logits, const int64_t* labels, int6
 hipError_t launch_softmax_xent_opts(int dt, void* logits, const int64_t* labels, int64_t n, int64_t vp, int v,
                                     float* loss, float eps, float zeta, int variant, hipStream_t st);
 
+// ---- LM head scoring, forward only (lm_score.hip): read-only logits [n, vp], real columns j < v
+// row_loss = lse - (1 - eps) x_y - eps mean(x) + zeta lse^2 (0 for a label outside [0, v)), row_lse = logsumexp,
+// pred = lowest column of the row maximum, rank = #{x_j > x_y} + #{j < y : x_j == x_y} (-1 for an ignored row)
+hipError_t launch_lm_score(int dt, const void* logits, const int64_t* labels, int64_t n, int64_t vp, int v, float eps,
+                           float zeta, float* row_loss, float* row_lse, int* pred, int* rank, hipStream_t st);
+
 }  // namespace dlion

@@ -30,6 +30,7 @@ from transformers.modeling_outputs import CausalLMOutputWithCrossAttentions
 from ..ops import fused
 from ..ops.linear import linear_kn, no_wgrad_deferral_this_window
 from .loss_options import LossOptionsMixin
+from .scoring import scored_output
 
 GPT2_SIZES = {
     "gpt2": dict(n_embd=768, n_layer=12, n_head=12),
@@ -210,8 +211,10 @@ class GPT2LMHeadModel(LossOptionsMixin, PreTrainedModel):
         self.transformer.gradient_checkpointing = False
 
     def forward(self, input_ids=None, labels=None, attention_mask=None, num_items_in_batch=None,
-                return_dict: Optional[bool] = None, **kwargs):
+                return_dict: Optional[bool] = None, predictions: bool = False, **kwargs):
         h = self.transformer(input_ids)
+        if predictions:  # evaluation without logits: loss, top-1 token and label rank per position
+            return scored_output(self, h, self.lm_head.weight, labels, num_items_in_batch)
         loss = None
         logits = None
         if labels is not None:

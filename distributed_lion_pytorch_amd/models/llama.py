@@ -22,6 +22,7 @@ from transformers.modeling_outputs import CausalLMOutputWithPast
 from ..ops import fused
 from ..ops.linear import linear_multi_nk, linear_nk, no_wgrad_deferral_this_window
 from .loss_options import LossOptionsMixin
+from .scoring import scored_output
 
 LLAMA_SIZES = {
     "llama-2-7b": dict(hidden_size=4096, intermediate_size=11008, num_hidden_layers=32, num_attention_heads=32,
@@ -356,10 +357,12 @@ class LlamaForCausalLM(LossOptionsMixin, PreTrainedModel):
         self.model.gradient_checkpointing = False
 
     def forward(self, input_ids=None, labels=None, attention_mask=None, num_items_in_batch=None,
-                return_dict: Optional[bool] = None, position_ids=None, **kwargs):
+                return_dict: Optional[bool] = None, position_ids=None, predictions: bool = False, **kwargs):
         # position_ids is a named parameter: HF's remove_unused_columns keeps only
         # those.  They switch on document-isolated attention (LlamaModel.forward).
         h = self.model(input_ids, position_ids)
+        if predictions:  # evaluation without logits: loss, top-1 token and label rank per position
+            return scored_output(self, h, self.lm_head.weight, labels, num_items_in_batch)
         loss = logits = None
         if labels is not None:
             loss = fused.causal_lm_loss(h, self.lm_head.weight, labels, normalizer=num_items_in_batch,

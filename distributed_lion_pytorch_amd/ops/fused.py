@@ -12,7 +12,8 @@ implementation is chosen per call:
 """
 from __future__ import annotations
 
-
+import contextlib
+from typing import NamedTuple
 
 import torch
 import torch.nn.functional as F
@@ -1694,6 +1695,111 @@ def causal_lm_loss(h: torch.Tensor, weight: torch.Tensor, labels: torch.Tensor, 
     """Shifted next-token cross-entropy of the LM head on h [B, T, C]."""
     return lm_head_cross_entropy(h, weight, shift_labels(labels), normalizer=normalizer,
                                  label_smoothing=label_smoothing, z_loss=z_loss)
+
+
+# --------------------------------------------- LM head scoring (forward only)
+class LMScore(NamedTuple):
+    """What :func:`lm_head_score` returns: the scalar ``loss``, the fp32 per-row
+    ``row_loss`` and ``lse`` [N], and ``pred`` / ``rank`` (int32, shaped like the labels)."""
+
+    loss: torch.Tensor
+    row_loss: torch.Tensor
+    lse: torch.Tensor
+    pred: torch.Tensor
+    rank: torch.Tensor
+
+
+_SCORE_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
+
+
+def _lm_score_torch(logits: torch.Tensor, labels: torch.Tensor, v: int, label_smoothing: float = 0.0,
+                    z_loss: float = 0.0):
+    """PyTorch form of the scoring kernel (csrc/lm_score.hip) on logits [N, Vp],
+    real columns j < v: fp32 (row_loss, lse), int32 (pred, rank).  ``pred`` is the
+    lowest column holding the row maximum (compared as floats), ``rank`` the
+    number of columns with a greater value than the label's plus the equal ones
+    at a lower column; rows whose label is outside [0, v) give loss 0, rank -1."""
+    x = logits[:, :v].float()
+    lse = torch.logsumexp(x, dim=1)
+    valid = (labels >= 0) & (labels < v)
+    safe = labels.clamp(0, v - 1)
+    tgt = x.gather(1, safe[:, None])
+    eps, z = float(label_smoothing), float(z_loss)
+    row = lse - (1.0 - eps) * tgt.squeeze(1) + z * lse * lse
+    if eps != 0.0:
+        row = row - eps * x.mean(dim=1)
+    row_loss = torch.where(valid, row, torch.zeros_like(lse))
+    cols = torch.arange(v, device=x.device)
+    first = torch.where(x == x.max(dim=1, keepdim=True).values, cols, cols.new_full((), v)).min(dim=1).values
+    pred = first.clamp_max(v - 1).to(torch.int32)  # a NaN maximum equals nothing: still a column of the row
+    before = (x > tgt) | ((x == tgt) & (cols < safe[:, None]))
+    rank = torch.where(valid, before.sum(dim=1), torch.full_like(safe, -1)).to(torch.int32)
+    return row_loss, lse, pred, rank
+
+
+def lm_head_score(h: torch.Tensor, weight: torch.Tensor, labels: torch.Tensor, label_smoothing: float = 0.0,
+                  z_loss: float = 0.0, normalizer=None) -> LMScore:
+    """Evaluate the LM head ``h @ weight.T`` against ``labels`` (-100 ignored)
+    without keeping logits: one GEMM into a transient [N, Vp] block and one
+    read-only kernel pass over it.  Returns :class:`LMScore`: ``loss`` as
+    :func:`lm_head_cross_entropy` defines it (mean over valid tokens, or sum /
+    ``normalizer``; same ``label_smoothing`` / ``z_loss``), the per-row loss and
+    logsumexp, the top-1 token ``pred`` (ties: the lowest id, as ``argmax``) and
+    the label's ``rank`` (0 exactly when ``pred`` is the label, -1 where it is
+    ignored; ``rank < k`` is top-k accuracy).  Forward only: it runs under
+    ``torch.no_grad`` and raises if called where a gradient would be recorded."""
+    eps, z = check_loss_options(label_smoothing, z_loss)
+    if torch.is_grad_enabled() and (h.requires_grad or weight.requires_grad):
+        raise RuntimeError("dlion: lm_head_score is forward-only (no gradient reaches h or the weight); "
+                           "call it under torch.no_grad(), or use lm_head_cross_entropy to train")
+    with torch.no_grad():
+        h2d = h.reshape(-1, h.shape[-1])
+        labels1d = labels.reshape(-1)
+        v = weight.shape[0]
+        if h2d.is_cuda:
+            from .linear import autocast_inputs
+
+            h2d, weight = autocast_inputs(h2d, weight)
+        elif h2d.dtype != weight.dtype:
+            h2d = h2d.to(weight.dtype)
+        with torch.autocast("cuda", enabled=False) if h2d.is_cuda else contextlib.nullcontext():
+            logits = gemm_fwd(h2d, _pad_rows(weight))  # [N, Vp] in the compute dtype, read once below
+            if normalizer is None:
+                n_valid = (labels1d != -100).sum().clamp_min(1).to(torch.float32)
+            else:
+                n_valid = torch.as_tensor(normalizer, dtype=torch.float32, device=h2d.device).clamp_min(1)
+            check_labels(labels1d, v)
+            if logits.dtype in _SCORE_DTYPES and _use_hip(logits):
+                row_loss, lse, pred, rank = hip.ops().lm_score(logits.contiguous(), labels1d.contiguous(), v, eps, z)
+            else:
+                row_loss, lse, pred, rank = _lm_score_torch(logits, labels1d, v, eps, z)
+            del logits
+        return LMScore(row_loss.sum() / n_valid, row_loss, lse, pred.view(labels.shape), rank.view(labels.shape))
+
+
+def causal_lm_score(h: torch.Tensor, weight: torch.Tensor, labels: torch.Tensor, normalizer=None,
+                    label_smoothing: float = 0.0, z_loss: float = 0.0) -> LMScore:
+    """:func:`lm_head_score` of h [B, T, C] against the shifted labels: ``pred[:, t]``
+    is the model's token for position t + 1 and ``rank[:, t]`` refers to
+    ``labels[:, t + 1]`` (-1 at t = T - 1 and where that label is -100)."""
+    return lm_head_score(h, weight, shift_labels(labels), label_smoothing=label_smoothing, z_loss=z_loss,
+                         normalizer=normalizer)
+
+
+def token_predictions(logits, labels=None):
+    """``preprocess_logits_for_metrics`` of the package: the (predictions,
+    label_ranks) pair of a scored evaluation step passes through; full logits
+    [B, T, V] (a model without the scoring path) are reduced to the same pair in
+    PyTorch, aligned as :func:`causal_lm_score` aligns them."""
+    if isinstance(logits, (tuple, list)):
+        if len(logits) == 2 and all(torch.is_tensor(t) and not t.is_floating_point() for t in logits):
+            return tuple(logits)
+        logits = logits[0]
+    if labels is None:
+        raise ValueError("dlion: token_predictions needs the labels to rank them in a logits tensor")
+    v = logits.shape[-1]
+    _, _, pred, rank = _lm_score_torch(logits.reshape(-1, v), shift_labels(labels).reshape(-1), v)
+    return pred.view(labels.shape), rank.view(labels.shape)
 
 
 def reference_lm_loss(h, weight, labels):

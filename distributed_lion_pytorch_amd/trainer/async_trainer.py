@@ -26,6 +26,7 @@ Re-designed for the installed transformers 5.x:
 from __future__ import annotations
 
 import contextlib
+import inspect
 import logging
 import os
 from dataclasses import dataclass, field
@@ -35,6 +36,7 @@ import torch
 import torch.distributed as dist
 from transformers import Trainer, TrainingArguments
 
+from ..ops.fused import token_predictions
 from ..optim.lion import Lion
 
 logger = logging.getLogger(__name__)
@@ -113,6 +115,9 @@ class AsyncTrainingArguments(TrainingArguments, LionArguments):
     async_grad: bool = field(default=False, metadata={
         "help": "compute gradients per worker and never combine them (sync only via Lion's vote)"})
     synthetic_data: bool = field(default=False, metadata={"help": "train on synthetic token ids (offline)"})
+    fused_eval: bool = field(default=True, metadata={
+        "help": "evaluate native models without logits: loss, top-1 token and label rank from one fused pass over "
+                "the LM head (ScoredEvalMixin); False keeps the [B, T, V] logits path"})
 
 
 def parse_dropout_schedule(spec: Optional[str]) -> dict:
@@ -570,11 +575,48 @@ class RankShardedLoaderMixin:
         return super().get_train_dataloader()
 
 
-class AsyncTrainer(AsyncMixin, RankShardedLoaderMixin, Trainer):
+class ScoredEvalMixin:
+    """Evaluation of a native model without logits.  ``prediction_step`` calls
+    ``model(**inputs, predictions=True)`` -- the LM head runs once, through
+    ops/fused.causal_lm_score -- and hands the loop ``(loss, (predictions,
+    label_ranks), labels)``, or ``(loss, None, None)`` for a loss-only
+    evaluation.  It is taken when the unwrapped model's ``forward`` has the
+    ``predictions`` keyword, the batch has labels, ``--fused_eval`` is on (the
+    default) and either only the loss is wanted or the trainer's
+    ``preprocess_logits_for_metrics`` is the package's own
+    :func:`token_predictions`: nobody else then sees logits.  Every other case
+    (a stock HF model, a user's ``preprocess_logits_for_metrics``, HF's label
+    smoother) is HF's ``prediction_step`` untouched."""
+
+    def _scored_eval(self, model, inputs, prediction_loss_only) -> bool:
+        if not getattr(self.args, "fused_eval", True) or getattr(self, "label_smoother", None) is not None:
+            return False
+        if inputs.get("labels") is None:
+            return False
+        if not (prediction_loss_only or self.preprocess_logits_for_metrics is token_predictions):
+            return False
+        inner = model
+        while hasattr(inner, "module"):
+            inner = inner.module
+        try:
+            return "predictions" in inspect.signature(inner.forward).parameters
+        except (TypeError, ValueError):
+            return False
+
+    def prediction_step(self, model, inputs, prediction_loss_only, ignore_keys=None):
+        if self._scored_eval(model, inputs, prediction_loss_only):
+            # HF's own step with one more keyword for the model: its loss handling (num_items_in_batch
+            # included) stays what it is, and the output's non-loss fields -- logits is None and
+            # dropped -- come back as the "logits": (predictions, label_ranks)
+            inputs = {**inputs, "predictions": True}
+        return super().prediction_step(model, inputs, prediction_loss_only, ignore_keys=ignore_keys)
+
+
+class AsyncTrainer(AsyncMixin, RankShardedLoaderMixin, ScoredEvalMixin, Trainer):
     """HF Trainer without gradient all-reduce (reference async_trainer.py:8-34)."""
 
 
-class LocalTrainer(RankShardedLoaderMixin, Trainer):
+class LocalTrainer(RankShardedLoaderMixin, ScoredEvalMixin, Trainer):
     """Stock HF Trainer (DDP gradient all-reduce, the reference's path without
     ``--async_grad``) that also takes rank-sharded streams."""
 

@@ -15,7 +15,7 @@ from transformers import Trainer, default_data_collator
 
 from ..models.lora import LoraConfig, inject_lora
 from ..utils.data import ConstantLengthDataset, prepare_sample_text
-from .async_trainer import AsyncMixin, RankShardedLoaderMixin
+from .async_trainer import AsyncMixin, RankShardedLoaderMixin, ScoredEvalMixin
 
 
 def _is_packed(ds) -> bool:
@@ -28,7 +28,7 @@ def _is_packed(ds) -> bool:
     return isinstance(item, dict) and "input_ids" in item
 
 
-class SFTTrainer(RankShardedLoaderMixin, Trainer):
+class SFTTrainer(RankShardedLoaderMixin, ScoredEvalMixin, Trainer):
     def __init__(self, model=None, args=None, train_dataset=None, eval_dataset=None, tokenizer=None,
                  processing_class=None, peft_config: Optional[LoraConfig] = None, packing: bool = True,
                  max_seq_length: int = 1024, formatting_func: Optional[Callable] = None, data_collator=None,

@@ -36,6 +36,7 @@ from transformers.trainer_utils import get_last_checkpoint
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+from distributed_lion_pytorch_amd import token_predictions  # noqa: E402
 from distributed_lion_pytorch_amd.models.registry import build_model, load_config  # noqa: E402
 from distributed_lion_pytorch_amd.trainer.async_trainer import (  # noqa: E402
     AsyncTrainer, AsyncTrainingArguments, LocalTrainer, build_lion, warn_unsynced)
@@ -221,17 +222,19 @@ def main(argv=None):
     train_ds, eval_ds = build_datasets(data_args, training_args, tokenizer, model.config.vocab_size, block_size,
                                        cache_dir=model_args.cache_dir)
 
-    def preprocess_logits_for_metrics(logits, labels):
-        if isinstance(logits, tuple):
-            logits = logits[0]
-        return logits.argmax(dim=-1)
+    # token_predictions: a native model hands (top-1 token, label rank) per position straight from the fused
+    # LM-head scoring pass (no [B, T, V] logits; --fused_eval False: the logits path); full logits of any other
+    # model are reduced to the same pair
+    preprocess_logits_for_metrics = token_predictions
 
     def compute_metrics(eval_preds):  # token accuracy (evaluate.load("accuracy") offline-free)
-        preds, labels = eval_preds
+        (preds, ranks), labels = eval_preds
         labels = labels[:, 1:].reshape(-1)
         preds = preds[:, :-1].reshape(-1)
+        ranks = ranks[:, :-1].reshape(-1)  # ranks[:, t] is the rank of labels[:, t + 1]
         mask = labels != -100
-        return {"accuracy": float((preds[mask] == labels[mask]).mean())}
+        return {"accuracy": float((preds[mask] == labels[mask]).mean()),
+                "top5_accuracy": float((ranks[mask] < 5).mean())}
 
     optimizers = (None, None)
     if training_args.lion:

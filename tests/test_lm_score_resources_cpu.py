@@ -1,0 +1,81 @@
+"""Resource guard for the LM-head scoring kernels (CPU: hipcc cross-compiles
+csrc/lm_score.hip for gfx950 and reads -Rpass-analysis=kernel-resource-usage,
+the approach of tests/test_xent_resources_cpu.py): no scratch and no VGPR spill
+in any instantiation, and ``resource_table()`` is what
+profiles/r11/lm_score_resources.txt holds."""
+import re
+import shutil
+import subprocess
+from pathlib import Path
+
+import pytest
+
+ROOT = Path(__file__).resolve().parent.parent
+CSRC = ROOT / "distributed_lion_pytorch_amd" / "csrc"
+HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+
+
+def score_resources(tmp_path):
+    cmd = [HIPCC, "-O3", "--offload-arch=gfx950", "-std=c++17", f"-I{CSRC}", "--cuda-device-only", "-c",
+           str(CSRC / "lm_score.hip"), "-o", str(Path(tmp_path) / "lm_score.o"),
+           "-Rpass-analysis=kernel-resource-usage"]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out, name = {}, None
+    for line in r.stderr.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            name = m.group(1)
+            out[name] = {}
+            continue
+        m = re.search(r"remark: +([A-Za-z \[\]/]+): (\d+)", line)
+        if m and name:
+            out[name][m.group(1).strip()] = int(m.group(2))
+    return out
+
+
+def _short(name: str) -> str:
+    m = re.match(r"_ZN5dlion\d+(lm_score\w*?_kernel)ILi(\d+)E", name)
+    return f"{m.group(1)}<{m.group(2)}>" if m else name
+
+
+def resource_table(res) -> str:
+    head = f"{'kernel':24s} {'VGPRs':>5s} {'SGPRs':>5s} {'LDS':>5s} {'scratch':>7s} {'VGPR spill':>10s} {'SGPR spill':>10s} {'waves/SIMD':>10s}"
+    lines = ["# csrc/lm_score.hip for gfx950, -O3, -Rpass-analysis=kernel-resource-usage",
+             "# template argument: dtype (0 fp32, 1 bf16, 2 fp16)", head]
+    for k in sorted(res, key=_short):
+        v = res[k]
+        lines.append(f"{_short(k):24s} {v['VGPRs']:5d} {v['TotalSGPRs']:5d} {v['LDS Size [bytes/block]']:5d} "
+                     f"{v['ScratchSize [bytes/lane]']:7d} {v['VGPRs Spill']:10d} {v['SGPRs Spill']:10d} "
+                     f"{v['Occupancy [waves/SIMD]']:10d}")
+    return "\n".join(lines) + "\n"
+
+
+@pytest.fixture(scope="module")
+def res(tmp_path_factory):
+    if not Path(HIPCC).exists():
+        pytest.skip("hipcc not available")
+    return score_resources(tmp_path_factory.mktemp("lm_score"))
+
+
+def test_score_kernels_have_no_scratch_and_no_vgpr_spill(res):
+    kernels = {k: v for k, v in res.items() if "lm_score" in k}
+    assert len(kernels) == 3, sorted(_short(k) for k in kernels)  # one per dtype
+    bad = {_short(k): v for k, v in kernels.items() if v["ScratchSize [bytes/lane]"] or v["VGPRs Spill"]}
+    assert not bad, bad
+    # 512-thread blocks at full occupancy: four rows in flight per CU
+    for k, v in kernels.items():
+        assert v["VGPRs"] <= 64, (_short(k), v["VGPRs"])
+
+
+def test_recorded_table_is_current(res):
+    f = ROOT / "profiles" / "r11" / "lm_score_resources.txt"
+    assert f.read_text() == resource_table(res), "regenerate profiles/r11/lm_score_resources.txt (resource_table)"
+
+
+if __name__ == "__main__":  # regenerate the recorded table
+    import tempfile
+
+    with tempfile.TemporaryDirectory() as d:
+        (ROOT / "profiles" / "r11").mkdir(parents=True, exist_ok=True)
+        (ROOT / "profiles" / "r11" / "lm_score_resources.txt").write_text(resource_table(score_resources(d)))
