@@ -10,6 +10,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdlib>
 #include <string>
 #include <tuple>
@@ -1348,11 +1349,119 @@ void dequant4_t_(const Tensor& q, const Tensor& absmax, const Tensor& code, cons
                                      out.stride(0), cur_stream()),
             "dequant4_t");
 }
+
+// ---- generation (csrc/decode.hip)
+// x [B, heads, D] bf16 with contiguous heads and a 16-byte aligned row stride (a column view of the fused q|k|v
+// projection output of one token per sequence)
+void check_step_rows(const char* what, const char* name, const Tensor& x, int64_t B, int64_t D) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 3 && x.scalar_type() == at::kBFloat16 && x.size(0) == B && x.size(2) == D &&
+                  x.size(1) >= 1 && x.stride(2) == 1 && (x.size(1) == 1 || x.stride(1) == D) &&
+                  (B == 1 || (x.stride(0) % 8 == 0 && x.stride(0) >= x.size(1) * D)) &&
+                  reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "dlion ", what, ": ", name, " must be bf16 [B, heads, D] with contiguous heads and a 16-byte aligned row stride");
+}
+// cache [B, Tmax, Hkv, D] bf16, token-major: contiguous heads, token and batch strides that do not overlap
+void check_cache(const char* what, const char* name, const Tensor& c, int64_t B, int64_t Hkv, int64_t D) {
+  TORCH_CHECK(c.is_cuda() && c.dim() == 4 && c.scalar_type() == at::kBFloat16 && c.size(0) == B && c.size(1) >= 1 &&
+                  c.size(2) == Hkv && c.size(3) == D && c.stride(3) == 1 && (Hkv == 1 || c.stride(2) == D) &&
+                  (c.size(1) == 1 || (c.stride(1) % 8 == 0 && c.stride(1) >= Hkv * D)) &&
+                  (B == 1 || (c.stride(0) % 8 == 0 && c.stride(0) >= c.size(1) * (c.size(1) == 1 ? Hkv * D : c.stride(1)))) &&
+                  reinterpret_cast<uintptr_t>(c.data_ptr()) % 16 == 0 && c.size(1) < (int64_t{1} << 31),
+              "dlion ", what, ": ", name, " must be a token-major bf16 cache [B, Tmax, Hkv, D] with contiguous heads");
+}
+int64_t cache_token_stride(const Tensor& c) { return c.size(1) == 1 ? c.size(2) * c.size(3) : c.stride(1); }
+int64_t cache_batch_stride(const Tensor& c) { return c.size(0) == 1 ? c.size(1) * cache_token_stride(c) : c.stride(0); }
+int64_t step_row_stride(const Tensor& x) { return x.size(0) == 1 ? x.size(1) * x.size(2) : x.stride(0); }
+
+// returns the normed / rotated q [B, H, D]; k (normed / rotated) and v go to cache[b, pos[b]]
+Tensor kv_append(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& pos,
+                 const std::optional<Tensor>& cos, const std::optional<Tensor>& sin,
+                 const std::optional<Tensor>& q_gamma, const std::optional<Tensor>& k_gamma, double eps,
+                 const Tensor& k_cache, const Tensor& v_cache, const Tensor& err) {
+  TORCH_CHECK(q.dim() == 3, "dlion kv_append: q must be [B, H, D]");
+  const int64_t B = q.size(0), H = q.size(1), D = q.size(2);
+  TORCH_CHECK(D == 64 || D == 128, "dlion kv_append: head_dim must be 64 or 128");
+  TORCH_CHECK(k.dim() == 3 && v.dim() == 3 && k.size(1) == v.size(1), "dlion kv_append: k / v must be [B, Hkv, D]");
+  const int64_t Hkv = k.size(1);
+  check_step_rows("kv_append", "q", q, B, D);
+  check_step_rows("kv_append", "k", k, B, D);
+  check_step_rows("kv_append", "v", v, B, D);
+  check_cache("kv_append", "k_cache", k_cache, B, Hkv, D);
+  check_cache("kv_append", "v_cache", v_cache, B, Hkv, D);
+  const int64_t Tmax = k_cache.size(1);
+  TORCH_CHECK(v_cache.size(1) == Tmax, "dlion kv_append: the caches differ in length");
+  TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == at::kInt && pos.is_contiguous() && pos.numel() == B,
+              "dlion kv_append: pos must be a contiguous int32 [B] GPU tensor");
+  TORCH_CHECK(err.is_cuda() && err.scalar_type() == at::kInt && err.numel() >= 1, "dlion kv_append: err must be int32[1]");
+  TORCH_CHECK(cos.has_value() == sin.has_value() && q_gamma.has_value() == k_gamma.has_value() &&
+                  (!q_gamma.has_value() || cos.has_value()),
+              "dlion kv_append: cos / sin and q_gamma / k_gamma come as pairs, gains only with tables");
+  if (cos.has_value())
+    for (const Tensor* t : {&*cos, &*sin})
+      TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kBFloat16 && t->is_contiguous() && t->dim() == 2 &&
+                      t->size(0) >= Tmax && t->size(1) == D && reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                  "dlion kv_append: cos/sin must be contiguous bf16 [>= Tmax, D]");
+  if (q_gamma.has_value())
+    for (const Tensor* g : {&*q_gamma, &*k_gamma})
+      TORCH_CHECK(g->is_cuda() && g->scalar_type() == at::kBFloat16 && g->is_contiguous() && g->numel() == D &&
+                      reinterpret_cast<uintptr_t>(g->data_ptr()) % 16 == 0,
+                  "dlion kv_append: gains must be contiguous, 16-byte aligned bf16 [D]");
+  const c10::DeviceGuard dg(q.device());
+  auto q_out = at::empty({B, H, D}, q.options());
+  check_hip(dlion::launch_kv_append(
+                q.data_ptr(), k.data_ptr(), v.data_ptr(), step_row_stride(q), step_row_stride(k), step_row_stride(v),
+                pos.data_ptr<int>(), cos.has_value() ? cos->data_ptr() : nullptr,
+                sin.has_value() ? sin->data_ptr() : nullptr, q_gamma.has_value() ? q_gamma->data_ptr() : nullptr,
+                k_gamma.has_value() ? k_gamma->data_ptr() : nullptr, static_cast<float>(eps), q_out.data_ptr(),
+                k_cache.data_ptr(), v_cache.data_ptr(), cache_batch_stride(k_cache), cache_token_stride(k_cache),
+                cache_batch_stride(v_cache), cache_token_stride(v_cache), static_cast<int>(B), static_cast<int>(H),
+                static_cast<int>(Hkv), static_cast<int>(D), static_cast<int>(Tmax), err.data_ptr<int>(), cur_stream()),
+            "kv_append");
+  return q_out;
+}
+
+// out [B, H D]; splits / chunk from ops/fused.py decode_splits (a host rule over B, Hkv, max_len, window only)
+Tensor decode_attention(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const Tensor& kv_len,
+                        int64_t window, int64_t max_len, int64_t splits, int64_t chunk) {
+  TORCH_CHECK(q.dim() == 3 && k_cache.dim() == 4, "dlion decode_attention: q must be [B, H, D], the caches [B, Tmax, Hkv, D]");
+  const int64_t B = q.size(0), H = q.size(1), D = q.size(2), Tmax = k_cache.size(1), Hkv = k_cache.size(2);
+  TORCH_CHECK(D == 64 || D == 128, "dlion decode_attention: head_dim must be 64 or 128");
+  TORCH_CHECK(Hkv >= 1 && H % Hkv == 0 && H / Hkv <= 8, "dlion decode_attention: H / Hkv must be an integer in [1, 8]");
+  check_step_rows("decode_attention", "q", q, B, D);
+  check_cache("decode_attention", "k_cache", k_cache, B, Hkv, D);
+  check_cache("decode_attention", "v_cache", v_cache, B, Hkv, D);
+  TORCH_CHECK(v_cache.size(1) == Tmax, "dlion decode_attention: the caches differ in length");
+  TORCH_CHECK(kv_len.is_cuda() && kv_len.scalar_type() == at::kInt && kv_len.is_contiguous() && kv_len.numel() == B,
+              "dlion decode_attention: kv_len must be a contiguous int32 [B] GPU tensor");
+  TORCH_CHECK(max_len >= 1 && max_len < (int64_t{1} << 31) && window >= 0 && window < (int64_t{1} << 31) &&
+                  splits >= 1 && splits <= dlion::kDecodeMaxSplits && chunk >= 1 && chunk < (int64_t{1} << 31) &&
+                  B <= 65535 && Hkv <= 65535,
+              "dlion decode_attention: bad max_len / window / splits / chunk / batch");
+  const c10::DeviceGuard dg(q.device());
+  const auto f32 = q.options().dtype(at::kFloat);
+  auto part_ml = at::empty({2, B, H, splits}, f32);
+  auto part_o = at::empty({B, H, splits, D}, f32);
+  auto out = at::empty({B, H * D}, q.options());
+  float* pm = part_ml.data_ptr<float>();
+  check_hip(dlion::launch_decode_attention(
+                q.data_ptr(), step_row_stride(q), k_cache.data_ptr(), cache_batch_stride(k_cache),
+                cache_token_stride(k_cache), v_cache.data_ptr(), cache_batch_stride(v_cache), cache_token_stride(v_cache),
+                kv_len.data_ptr<int>(), pm, pm + B * H * splits, part_o.data_ptr<float>(), out.data_ptr(),
+                static_cast<int>(B), static_cast<int>(H), static_cast<int>(Hkv), static_cast<int>(D),
+                static_cast<int>(Tmax), static_cast<int>(max_len), static_cast<int>(window), static_cast<int>(splits),
+                static_cast<int>(chunk), 1.0f / std::sqrt(static_cast<float>(D)), cur_stream()),
+            "decode_attention");
+  return out;
+}
 }  // namespace
 
 TORCH_LIBRARY(dlion, m) {
   m.def("dequant4_t_(Tensor q, Tensor absmax, Tensor code, Tensor(a!) out) -> ()");
   m.def("transpose_pad(Tensor x, int rows_out=-1) -> Tensor");
+  m.def("kv_append(Tensor q, Tensor k, Tensor v, Tensor pos, Tensor? cos, Tensor? sin, Tensor? q_gamma, Tensor? k_gamma,"
+        " float eps, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor(c!) err) -> Tensor");
+  m.def("decode_attention(Tensor q, Tensor k_cache, Tensor v_cache, Tensor kv_len, int window, int max_len, int splits,"
+        " int chunk) -> Tensor");
   m.def("quant4(Tensor w, Tensor code) -> (Tensor, Tensor)");
   m.def("dequant4_(Tensor q, Tensor absmax, Tensor code, Tensor(a!) out) -> ()");
   m.def("gemm_tn(Tensor[] P, Tensor[] Q, int splits) -> Tensor");
@@ -1487,4 +1596,6 @@ TORCH_LIBRARY_IMPL(dlion, CUDA, m) {
   m.impl("dequant4_", &dequant4_);
   m.impl("dequant4_t_", &dequant4_t_);
   m.impl("transpose_pad", &transpose_pad);
+  m.impl("kv_append", &kv_append);
+  m.impl("decode_attention", &decode_attention);
 }

@@ -9,6 +9,7 @@
 // sum_partials reduces split-K / per-block fp32 partials [S][n] straight to
 // bf16 (one pass instead of ATen sum + dtype copy).
 #include "common.h"
+#include "rope_norm.h"
 
 namespace dlion {
 
@@ -336,13 +337,11 @@ __global__ void __launch_bounds__(256) rope_kernel(const uint16_t* x, const uint
     load4(sn + static_cast<int64_t>(t) * D + d0, sa);
     load4(sn + static_cast<int64_t>(t) * D + hd + d0, sb);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
+    for (int j = 0; j < 4; ++j) {  // rope_norm.h: the arithmetic is shared with decode.hip
       if (!inverse) {
-        oa[j] = a[j] * ca[j] - b[j] * sa[j];
-        ob[j] = b[j] * cb[j] + a[j] * sb[j];
+        rope_forward(a[j], b[j], ca[j], cb[j], sa[j], sb[j], oa[j], ob[j]);
       } else {
-        oa[j] = a[j] * ca[j] + b[j] * sb[j];
-        ob[j] = b[j] * cb[j] - a[j] * sa[j];
+        rope_inverse(a[j], b[j], ca[j], cb[j], sa[j], sb[j], oa[j], ob[j]);
       }
     }
     store4(y + oy + d0, oa);

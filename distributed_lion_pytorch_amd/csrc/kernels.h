@@ -102,7 +102,8 @@ hipError_t launch_gemm_nt(const void* A, int lda, const void* B, int ldb, void* 
 hipError_t launch_embed_fwd(const int64_t* ids, const void* wte, const void* wpe, void* out, int64_t n, int C, int T,
                             int64_t V, uint32_t seed, uint32_t thresh16, float inv_keep, int32_t* err, hipStream_t st);
 // error-flag bits (index_check / embed_fwd): OR-ed into err[0]
-constexpr int kIndexErrEmbed = 1, kIndexErrLabel = 2;
+// (4 is the host's position_ids check, ops/fused.py; 8 a cache position outside [0, Tmax), decode.hip)
+constexpr int kIndexErrEmbed = 1, kIndexErrLabel = 2, kIndexErrCache = 8;
 hipError_t launch_index_check(const int64_t* ids, int64_t n, int64_t hi, int64_t ignore, int32_t* err, int code,
                               hipStream_t st);
 // dwte / dwpe nullable; sid / perm = stably sorted ids and their positions (needed with dwte)
@@ -174,5 +175,24 @@ hipError_t launch_softmax_xent_opts(int dt, void* logits, const int64_t* labels,
 // pred = lowest column of the row maximum, rank = #{x_j > x_y} + #{j < y : x_j == x_y} (-1 for an ignored row)
 hipError_t launch_lm_score(int dt, const void* logits, const int64_t* labels, int64_t n, int64_t vp, int v, float eps,
                            float zeta, float* row_loss, float* row_lse, int* pred, int* rank, hipStream_t st);
+
+// ---- generation (decode.hip); bf16, D in {64, 128}
+// One decode step's q [B, H, D] / k / v [B, Hkv, D] (row strides *_ld, heads contiguous): q and k normed (gains
+// nullable, Qwen3) and rotated (tables [>= Tmax, D], nullable) at pos[b], clamped into [0, Tmax) with
+// kIndexErrCache OR-ed into err[0]; q to q_out [B, H, D], k and v to cache[b, pos[b]] of the token-major caches
+// (batch / token strides *_bs / *_ts, heads contiguous).
+hipError_t launch_kv_append(const void* q, const void* k, const void* v, int64_t q_ld, int64_t k_ld, int64_t v_ld,
+                            const int* pos, const void* cos, const void* sin, const void* q_gamma,
+                            const void* k_gamma, float eps, void* q_out, void* k_cache, void* v_cache, int64_t kc_bs,
+                            int64_t kc_ts, int64_t vc_bs, int64_t vc_ts, int B, int H, int Hkv, int D, int Tmax,
+                            int32_t* err, hipStream_t st);
+// out [B, H D]: row b attends the keys [max(0, len - window), len) of its cache, len = min(kv_len[b], max_len,
+// Tmax) (window 0: all).  splits blocks of chunk keys per (kv head, row), splits chunk >= min(window, max_len);
+// fp32 partials part_m / part_l [B, H, splits], part_o [B, H, splits, D], reduced by a combine pass.
+constexpr int kDecodeMaxSplits = 64;
+hipError_t launch_decode_attention(const void* q, int64_t q_ld, const void* k_cache, int64_t k_bs, int64_t k_ts,
+                                   const void* v_cache, int64_t v_bs, int64_t v_ts, const int* kv_len, float* part_m,
+                                   float* part_l, float* part_o, void* out, int B, int H, int Hkv, int D, int Tmax,
+                                   int max_len, int window, int splits, int chunk, float scale, hipStream_t st);
 
 }  // namespace dlion

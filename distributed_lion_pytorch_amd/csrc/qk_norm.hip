@@ -20,6 +20,7 @@
 // (read again, never stored), so the lanes a DPP move reads are always active.
 #include "common.h"
 #include "kernels.h"
+#include "rope_norm.h"
 
 // No implicit FMA contraction in this file: the arithmetic of a head row must not depend on which unrolled
 // slot of the backward's head loop it lands in (the compiler is free to fuse different products in each), or
@@ -31,47 +32,6 @@ namespace dlion {
 namespace {
 
 using E = Elem<kBF16>;
-
-constexpr int kQuadXor1 = 0xB1;     // quad_perm [1,0,3,2]
-constexpr int kQuadXor2 = 0x4E;     // quad_perm [2,3,0,1]
-constexpr int kQuadRev = 0x1B;      // quad_perm [3,2,1,0]
-constexpr int kRowRor8 = 0x128;     // lane i <- lane (i + 8) % 16
-constexpr int kHalfMirror = 0x141;  // lane i <- lane 7 - i of its 8
-constexpr int kRowMirror = 0x140;   // lane i <- lane 15 - i of its 16
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, false));
-}
-
-// sum over the LANES lanes of a head row, bit-identical in all of them
-template <int LANES>
-__device__ __forceinline__ float head_sum(float v) {
-  v += dpp_mov<kQuadXor1>(v);
-  v += dpp_mov<kQuadXor2>(v);
-  v += dpp_mov<kHalfMirror>(v);
-  if (LANES == 16) v += dpp_mov<kRowMirror>(v);
-  return v;
-}
-
-// the value of lane ^ (LANES / 2): the lane that holds the rotate-half partners
-template <int LANES>
-__device__ __forceinline__ float partner(float v) {
-  if (LANES == 16) return dpp_mov<kRowRor8>(v);
-  return dpp_mov<kQuadRev>(dpp_mov<kHalfMirror>(v));
-}
-
-__device__ __forceinline__ float dot8(const float (&a)[8], const float (&b)[8]) {
-  return ((a[0] * b[0] + a[1] * b[1]) + (a[2] * b[2] + a[3] * b[3])) +
-         ((a[4] * b[4] + a[5] * b[5]) + (a[6] * b[6] + a[7] * b[7]));
-}
-
-// v_rsq_f32 is good to 1 ulp; one Newton step leaves about half of one
-__device__ __forceinline__ float rsqrt_nr(float v) {
-  const float r = __builtin_amdgcn_rsqf(v);
-  const float e = __builtin_fmaf(-(v * r), r, 1.f);
-  return __builtin_fmaf(0.5f * r, e, r);
-}
 
 __device__ __forceinline__ void store8f(float* p, const float (&o)[8]) {
   reinterpret_cast<float4*>(p)[0] = make_float4(o[0], o[1], o[2], o[3]);
@@ -98,19 +58,14 @@ __global__ void __launch_bounds__(256) qk_norm_rope_fwd_kernel(
     const int64_t row = hrc / Hx;
     const int h = static_cast<int>(hrc - row * Hx);
     const int64_t tb = (row % T) * D + d0;
-    float v[8], c[8], s[8], yv[8], o[8];
+    float v[8], c[8], s[8], w[8], o[8];
     E::load8(x + row * x_ld + static_cast<int64_t>(h) * D + d0, v);
     E::load8(cs + tb, c);
     E::load8(sn + tb, s);
-    const float r = rsqrt_nr(head_sum<LANES>(dot8(v, v)) * (1.f / D) + eps);
     const bool a = h < split;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) yv[j] = (v[j] * r) * (a ? wa[j] : wb[j]);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float p = partner<LANES>(yv[j]);
-      o[j] = yv[j] * c[j] + (first ? -p : p) * s[j];
-    }
+    for (int j = 0; j < 8; ++j) w[j] = a ? wa[j] : wb[j];
+    const float r = qk_norm_rope_row<LANES>(v, w, c, s, eps, first, o);  // rope_norm.h, shared with decode.hip
     if (valid) {
       E::store8(y + hr * D + d0, o);
       if (sub == 0) rstd[hr] = r;

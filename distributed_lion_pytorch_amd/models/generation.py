@@ -1,0 +1,208 @@
+"""Generation for the native causal LMs: a token-major KV cache and ``generate``.
+
+``KVCache`` holds, per layer, k / v buffers ``[B, max_len, Hkv, D]`` -- the layout the training path computes
+k and v in, so the prefill writes them with plain copies -- and the per-row lengths on the device.  The models
+take it as an optional ``cache`` argument (models/llama.py, models/gpt2.py): the first call is the prefill (the
+prompt through the flash forward), every later call one decode step (one token per row through
+``fused.kv_append`` and ``fused.decode_attention``, csrc/decode.hip).
+
+``NativeGenerateMixin.generate`` uses HF's argument names: greedy or sampled (temperature, then top-k, then
+top-p), ragged prompts by ``attention_mask`` (left- or right-padded), EOS / pad handling.  Out of scope: beam
+search, repetition penalties, a paged or rolling cache (a windowed layer keeps its full-length cache and only
+bounds the key range), graph capture, speculative decoding.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import torch
+import torch.nn.functional as F
+
+from ..ops import fused
+
+_EOS_CHECK_EVERY = 8  # decode steps between two host reads of "every row has finished"
+
+
+def cache_geometry(config):
+    """(layers, kv heads, head_dim) of a GPT-2 or Llama-family config."""
+    if getattr(config, "model_type", "") == "gpt2":
+        return config.n_layer, config.n_head, config.n_embd // config.n_head
+    hd = getattr(config, "head_dim", None) or config.hidden_size // config.num_attention_heads
+    return config.num_hidden_layers, config.num_key_value_heads, hd
+
+
+class KVCache:
+    """Per-layer key / value buffers [B, max_len, Hkv, D] and the rows' lengths (int32, on the device).
+    Allocated once per ``generate`` call.  ``width`` is the host's bound on the lengths (prompt width plus
+    steps taken): it sizes the decode grid and refuses a step past ``max_len`` without a device sync."""
+
+    def __init__(self, config, batch: int, max_len: int, device=None, dtype=torch.float32):
+        layers, hkv, hd = cache_geometry(config)
+        self.batch, self.max_len = int(batch), int(max_len)
+        if self.batch < 1 or self.max_len < 1:
+            raise ValueError("KVCache: batch and max_len must be positive")
+        # one allocation: [layer, k | v, B, max_len, Hkv, D]
+        self._buf = torch.zeros(layers, 2, self.batch, self.max_len, hkv, hd, device=device, dtype=dtype)
+        self.lengths = torch.zeros(self.batch, dtype=torch.int32, device=device)
+        self.kv_len = self.lengths  # lengths + 1 during a decode step
+        self.width = 0
+        self.prefilled = False
+
+    def layer(self, i: int):
+        """(k, v) of layer i, each [B, max_len, Hkv, D]."""
+        return self._buf[i, 0], self._buf[i, 1]
+
+    def begin(self, B: int, T: int) -> bool:
+        """Start a forward of T tokens per row; True for the prefill (the first call)."""
+        if B != self.batch:
+            raise ValueError(f"KVCache: built for batch {self.batch}, got {B}")
+        if torch.is_grad_enabled():
+            raise RuntimeError("KVCache: the cached forward is inference only; call it under torch.no_grad()")
+        if not self.prefilled:
+            if T > self.max_len:
+                raise ValueError(f"KVCache: a prompt of {T} tokens does not fit max_len {self.max_len}")
+            return True
+        if T != 1:
+            raise ValueError("KVCache: after the prefill a forward takes one token per row")
+        if self.width + 1 > self.max_len:
+            raise ValueError(f"KVCache: full ({self.max_len} positions)")
+        self.kv_len = self.lengths + 1
+        return False
+
+    def advance(self, T: int) -> None:
+        if not self.prefilled:
+            self.lengths.fill_(T)
+            self.width, self.prefilled = T, True
+        else:
+            self.lengths += 1
+            self.width += 1
+
+    def set_lengths(self, lengths: torch.Tensor) -> None:
+        """Ragged prompts, left-aligned in the prefill: row b holds ``lengths[b]`` <= width real tokens."""
+        self.lengths.copy_(lengths.to(self.lengths.dtype))
+
+
+# ------------------------------------------------------------------------------------------ prompts
+def left_align(input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor]):
+    """(ids with every row's tokens moved to the left edge, lengths [B]); the mask may be left- or right-padded
+    but must be one contiguous run of ones per row."""
+    B, T = input_ids.shape
+    if attention_mask is None:
+        return input_ids, torch.full((B,), T, dtype=torch.long, device=input_ids.device)
+    if attention_mask.shape != input_ids.shape:
+        raise ValueError("generate: attention_mask must have the shape of input_ids")
+    m = attention_mask.to(input_ids.device) != 0
+    n = m.sum(1)
+    start = m.to(torch.int8).argmax(1)
+    idx = torch.arange(T, device=input_ids.device)[None, :]
+    run = (idx >= start[:, None]) & (idx < (start + n)[:, None])
+    if bool((n == 0).any()) or not bool((run == m).all()):
+        raise ValueError("generate: attention_mask needs one contiguous, non-empty run of ones per row "
+                         "(left- or right-padded prompts)")
+    ids = input_ids.gather(1, (idx + start[:, None]).clamp_max(T - 1))
+    return torch.where(idx < n[:, None], ids, torch.zeros_like(ids)), n
+
+
+# ------------------------------------------------------------------------------------------ sampling
+def warp_logits(logits: torch.Tensor, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0) -> torch.Tensor:
+    """fp32 logits [B, V] after temperature, then top-k, then top-p (HF's order and definitions: top-p keeps the
+    smallest set of most likely tokens whose probability reaches top_p); removed tokens are -inf."""
+    logits = logits.float()
+    if temperature != 1.0:
+        logits = logits / float(temperature)
+    if top_k and 0 < int(top_k) < logits.shape[-1]:
+        kth = torch.topk(logits, int(top_k), dim=-1).values[:, -1:]
+        logits = logits.masked_fill(logits < kth, float("-inf"))
+    if top_p < 1.0:
+        srt, order = torch.sort(logits, dim=-1, descending=False)
+        remove = srt.softmax(-1).cumsum(-1) <= (1.0 - float(top_p))
+        remove[:, -1] = False
+        logits = logits.masked_fill(torch.zeros_like(remove).scatter(1, order, remove), float("-inf"))
+    return logits
+
+
+class NativeGenerateMixin:
+    """``generate`` for GPT2LMHeadModel and LlamaForCausalLM (Mistral, Qwen2 and Qwen3 inherit it).
+
+    Not named ``...GenerationMixin``: transformers' ``PreTrainedModel.can_generate`` looks for that substring in
+    the base classes and would then attach a ``generation_config`` and write ``generation_config.json`` on save;
+    checkpoints stay what they were."""
+
+    def _decoder(self):
+        return self.transformer if hasattr(self, "transformer") else self.model
+
+    @torch.no_grad()
+    def generate(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
+                 max_new_tokens: int = 20, do_sample: bool = False, temperature: float = 1.0, top_k: int = 0,
+                 top_p: float = 1.0, eos_token_id=None, pad_token_id: Optional[int] = None,
+                 seed: Optional[int] = None) -> torch.Tensor:
+        """[B, T0] prompts -> [B, T0 + n_new] long: the prompt exactly as given, then the new tokens.
+
+        Greedy takes the top-1 of ``fused.lm_head_score`` (the lowest id on ties, no [B, V] tensor); sampling
+        warps the last hidden states' logits (temperature, top-k, top-p) and draws with ``torch.multinomial``
+        from a generator seeded by ``seed``.  Rows that emitted ``eos_token_id`` (int or list) produce
+        ``pad_token_id`` (default: the first EOS id) from then on; generation ends once every row has finished
+        (read from the device every 8 steps; the result is trimmed to the step at which the last row finished)."""
+        if self.training:
+            raise ValueError("generate: the model is in training mode; call model.eval() first")
+        if input_ids.dim() != 2 or input_ids.shape[1] < 1:
+            raise ValueError("generate: input_ids must be [B, T0] with T0 >= 1")
+        max_new_tokens = int(max_new_tokens)
+        if max_new_tokens < 1:
+            raise ValueError("generate: max_new_tokens must be >= 1")
+        if do_sample and not temperature > 0:
+            raise ValueError("generate: temperature must be > 0")
+        if do_sample and not 0.0 < top_p <= 1.0:
+            raise ValueError("generate: top_p must be in (0, 1]")
+        B, T0 = input_ids.shape
+        total = T0 + max_new_tokens
+        cfg = self.config
+        if cfg.model_type == "gpt2" and total > cfg.n_positions:
+            raise ValueError(f"generate: {T0} prompt + {max_new_tokens} new tokens exceed GPT-2's {cfg.n_positions} "
+                             "learned positions (max_position_embeddings)")
+        dev = input_ids.device
+        eos = None
+        if eos_token_id is not None:
+            eos = torch.as_tensor([eos_token_id] if isinstance(eos_token_id, int) else list(eos_token_id), device=dev)
+            if pad_token_id is None:
+                pad_token_id = int(eos[0])
+        ids, lens = left_align(input_ids, attention_mask)
+        weight = self.lm_head.weight
+        cache = KVCache(cfg, B, total, dev, weight.dtype)
+        gen = None
+        if do_sample and seed is not None:
+            gen = torch.Generator(device=dev)
+            gen.manual_seed(int(seed))
+
+        base = self._decoder()
+        rows = torch.arange(B, device=dev)
+        h = base(ids, cache=cache)[rows, lens - 1]  # prefill: the hidden state of every row's last real token
+        cache.set_lengths(lens)
+        new = torch.empty(B, max_new_tokens, dtype=torch.long, device=dev)
+        finished = torch.zeros(B, dtype=torch.bool, device=dev)
+        done_at = torch.full((B,), max_new_tokens, dtype=torch.long, device=dev)  # the step a row emitted EOS at
+        ignore = torch.full((B,), -100, dtype=torch.long, device=dev)
+        for i in range(max_new_tokens):
+            if do_sample:
+                logits = warp_logits(F.linear(h, weight), temperature, top_k, top_p)
+                tok = torch.multinomial(logits.softmax(-1), 1, generator=gen)[:, 0]
+            else:
+                tok = fused.lm_head_score(h, weight, ignore).pred.long()
+            if eos is not None:
+                tok = torch.where(finished, torch.full_like(tok, pad_token_id), tok)
+                hit = torch.isin(tok, eos) & ~finished
+                done_at = torch.where(hit, torch.full_like(done_at, i), done_at)
+                finished = finished | hit
+            new[:, i] = tok
+            if i + 1 == max_new_tokens:
+                break
+            if eos is not None and (i + 1) % _EOS_CHECK_EVERY == 0 and bool(finished.all()):
+                break
+            h = base(tok[:, None], cache=cache)[:, 0]
+        n_new = i + 1
+        if eos is not None:
+            last = int(done_at.max())  # the one read at the end: the step the last row finished at
+            if last < max_new_tokens:
+                n_new = last + 1
+        fused.check_index_errors()
+        return torch.cat([input_ids, new[:, :n_new]], dim=1)

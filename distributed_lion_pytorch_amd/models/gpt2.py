@@ -29,6 +29,7 @@ from transformers.modeling_outputs import CausalLMOutputWithCrossAttentions
 
 from ..ops import fused
 from ..ops.linear import linear_kn, no_wgrad_deferral_this_window
+from .generation import NativeGenerateMixin
 from .loss_options import LossOptionsMixin
 from .scoring import scored_output
 
@@ -73,12 +74,32 @@ class Attention(nn.Module):
         self.c_proj = Conv1D(cfg.n_embd, cfg.n_embd)
         self.attn_pdrop = cfg.attn_pdrop
 
-    def forward(self, x, proj_bias: bool = True):
+    def forward(self, x, proj_bias: bool = True, cache=None):
         """proj_bias=False leaves c_proj's bias to the caller's fused
         residual+dropout+LayerNorm kernel (its gradient comes out of it too)."""
+        if cache is not None:
+            y = self._attend_cached(x, cache)
+            return self.c_proj(y) if proj_bias else linear_kn(y, self.c_proj.weight, None)
         y = fused.qkv_attention(x, self.c_attn.weight, self.c_attn.bias, self.n_head,
                                 self.attn_pdrop if self.training else 0.0)  # [B, T, C]
         return self.c_proj(y) if proj_bias else linear_kn(y, self.c_proj.weight, None)
+
+    def _attend_cached(self, x, cache):
+        """Generation (models/generation.py KVCache): the packed qkv split into its q | k | v column views.
+        Prefill: k and v copied into cache[:, :T], attention by the flash forward.  Decode step: a pure append
+        (no rotary tables) and fused.decode_attention over the cache."""
+        B, T, C = x.shape
+        H, D = self.n_head, self.head_dim
+        kc, vc = cache.layer(self.layer_idx)
+        qkv = self.c_attn(x)
+        if cache.prefilled:
+            q, k, v = (qkv[:, 0, j * C:(j + 1) * C].view(B, H, D) for j in range(3))
+            q = fused.kv_append(q, k, v, cache.lengths, None, None, None, None, 0.0, kc, vc)
+            return fused.decode_attention(q, kc, vc, cache.kv_len, 0, cache.width + 1).view(B, 1, C)
+        q, k, v = (qkv[..., j * C:(j + 1) * C].view(B, T, H, D) for j in range(3))
+        kc[:, :T].copy_(k)
+        vc[:, :T].copy_(v)
+        return fused.causal_attention_gqa(q, k, v)
 
 
 class MLP(nn.Module):
@@ -127,11 +148,15 @@ class GPT2Model(nn.Module):
         self.wte = nn.Embedding(cfg.vocab_size, cfg.n_embd)
         self.wpe = nn.Embedding(cfg.n_positions, cfg.n_embd)
         self.h = nn.ModuleList([Block(cfg) for _ in range(cfg.n_layer)])
+        for i, blk in enumerate(self.h):
+            blk.attn.layer_idx = i  # the layer's slot in a KVCache
         self.ln_f = nn.LayerNorm(cfg.n_embd, eps=cfg.layer_norm_epsilon)
         self.embd_pdrop = cfg.embd_pdrop
         self.gradient_checkpointing = False
 
-    def forward(self, input_ids):
+    def forward(self, input_ids, cache=None):
+        if cache is not None:
+            return self._forward_cached(input_ids, cache)
         p = self.embd_pdrop if self.training else 0.0
         x = fused.embed(input_ids, self.wte.weight, self.wpe.weight, p)  # gather + add + dropout, one kernel
         if self.gradient_checkpointing and self.training:
@@ -152,8 +177,27 @@ class GPT2Model(nn.Module):
                                           bias=blk.mlp.c_proj.bias)
         return h
 
+    def _forward_cached(self, input_ids, cache):
+        """The prefill (first call on a fresh KVCache: the whole prompt) or one decode step (one token per
+        row, at position lengths[b]) of generation, through the fused chain of ``forward`` without dropout."""
+        B, T = input_ids.shape
+        if cache.begin(B, T):
+            x = fused.embed(input_ids, self.wte.weight, self.wpe.weight, 0.0)
+        else:
+            x = F.embedding(input_ids, self.wte.weight) + F.embedding(cache.lengths.long(), self.wpe.weight)[:, None]
+        first = self.h[0].ln_1
+        h = fused.norm(x, first.weight, first.bias, first.eps)
+        for i, blk in enumerate(self.h):
+            x, h = fused.dropout_add_norm(blk.attn(h, proj_bias=False, cache=cache), x, blk.ln_2.weight, blk.ln_2.bias,
+                                          blk.ln_2.eps, 0.0, bias=blk.attn.c_proj.bias)
+            nxt = self.h[i + 1].ln_1 if i + 1 < len(self.h) else self.ln_f
+            x, h = fused.dropout_add_norm(blk.mlp(h, proj_bias=False), x, nxt.weight, nxt.bias, nxt.eps, 0.0,
+                                          bias=blk.mlp.c_proj.bias)
+        cache.advance(T)
+        return h
 
-class GPT2LMHeadModel(LossOptionsMixin, PreTrainedModel):
+
+class GPT2LMHeadModel(NativeGenerateMixin, LossOptionsMixin, PreTrainedModel):
     config_class = GPT2Config
     base_model_prefix = "transformer"
     _tied_weights_keys = {"lm_head.weight": "transformer.wte.weight"}
@@ -211,8 +255,9 @@ class GPT2LMHeadModel(LossOptionsMixin, PreTrainedModel):
         self.transformer.gradient_checkpointing = False
 
     def forward(self, input_ids=None, labels=None, attention_mask=None, num_items_in_batch=None,
-                return_dict: Optional[bool] = None, predictions: bool = False, **kwargs):
-        h = self.transformer(input_ids)
+                return_dict: Optional[bool] = None, predictions: bool = False, cache=None, **kwargs):
+        # cache (models/generation.py KVCache): the prefill or one decode step of generation
+        h = self.transformer(input_ids, cache)
         if predictions:  # evaluation without logits: loss, top-1 token and label rank per position
             return scored_output(self, h, self.lm_head.weight, labels, num_items_in_batch)
         loss = None

@@ -21,6 +21,7 @@ from transformers.modeling_outputs import CausalLMOutputWithPast
 
 from ..ops import fused
 from ..ops.linear import linear_multi_nk, linear_nk, no_wgrad_deferral_this_window
+from .generation import NativeGenerateMixin
 from .loss_options import LossOptionsMixin
 from .scoring import scored_output
 
@@ -161,6 +162,7 @@ def _layer_window(cfg, i: int) -> int:
 class LlamaAttention(nn.Module):
     def __init__(self, cfg: LlamaConfig, layer_idx: int = 0):
         super().__init__()
+        self.layer_idx = layer_idx  # the layer's slot in a KVCache
         self.window = _layer_window(cfg, layer_idx)  # 0: full causal
         self.n_head = cfg.num_attention_heads
         self.n_kv = cfg.num_key_value_heads
@@ -176,7 +178,9 @@ class LlamaAttention(nn.Module):
             self.q_norm = RMSNorm(self.head_dim, cfg.rms_norm_eps)
             self.k_norm = RMSNorm(self.head_dim, cfg.rms_norm_eps)
 
-    def forward(self, x, cos, sin, bounds=None):
+    def forward(self, x, cos, sin, bounds=None, cache=None):
+        if cache is not None:
+            return self._forward_cached(x, cos, sin, cache)
         B, T, _ = x.shape
         q, k, v = _proj(x, (self.q_proj, self.k_proj, self.v_proj))
         q = q.view(B, T, self.n_head, self.head_dim)
@@ -189,6 +193,33 @@ class LlamaAttention(nn.Module):
         else:
             y = fused.rope_attention(q, k, v, cos, sin, p, self.window, bounds)
         return _lin(self.o_proj, y)
+
+    def _forward_cached(self, x, cos, sin, cache):
+        """Generation (models/generation.py KVCache; cos / sin cover the cache's max_len).  Prefill: the prompt's
+        rotated k and v are copied into cache[:, :T] and attention is the flash forward.  Decode step (one token
+        per row): fused.kv_append rotates q and k at each row's own position and appends k and v, then
+        fused.decode_attention reads the cache once for the whole group of query heads."""
+        B, T, _ = x.shape
+        kc, vc = cache.layer(self.layer_idx)
+        q, k, v = _proj(x, (self.q_proj, self.k_proj, self.v_proj))
+        gq, gk, eps = (self.q_norm.weight, self.k_norm.weight, self.q_norm.eps) if hasattr(self, "q_norm") else (None, None, 0.0)
+        if cache.prefilled:
+            q = q[:, 0].view(B, self.n_head, self.head_dim)
+            k = k[:, 0].view(B, self.n_kv, self.head_dim)
+            v = v[:, 0].view(B, self.n_kv, self.head_dim)
+            q = fused.kv_append(q, k, v, cache.lengths, cos, sin, gq, gk, eps, kc, vc)
+            y = fused.decode_attention(q, kc, vc, cache.kv_len, self.window, cache.width + 1).view(B, 1, -1)
+            return _lin(self.o_proj, y)
+        q = q.view(B, T, self.n_head, self.head_dim)
+        k = k.view(B, T, self.n_kv, self.head_dim)
+        v = v.view(B, T, self.n_kv, self.head_dim)
+        if gq is not None:
+            q, k = fused.qk_norm_rope(q, gq, eps, cos, sin), fused.qk_norm_rope(k, gk, eps, cos, sin)
+        else:
+            q, k = fused.rope(q, cos, sin), fused.rope(k, cos, sin)
+        kc[:, :T].copy_(k)
+        vc[:, :T].copy_(v)
+        return _lin(self.o_proj, fused.causal_attention_gqa(q, k, v, 0.0, self.window))
 
 
 def _lin(layer: nn.Module, x):
@@ -280,7 +311,9 @@ class LlamaModel(nn.Module):
                 per_window[w] = fused.visibility_bounds(position_ids, w)
         return [per_window[layer.self_attn.window] for layer in self.layers]
 
-    def forward(self, input_ids, position_ids=None):
+    def forward(self, input_ids, position_ids=None, cache=None):
+        if cache is not None:
+            return self._forward_cached(input_ids, cache)
         T = input_ids.shape[1]
         x = self.embed_tokens(input_ids)
         # position_ids that restart per document (packed rows) bound every row's
@@ -306,8 +339,26 @@ class LlamaModel(nn.Module):
             x, h = fused.dropout_add_norm(layer.mlp(h), x, nxt.weight, None, nxt.eps, 0.0, rms=True)
         return h
 
+    def _forward_cached(self, input_ids, cache):
+        """The prefill (first call on a fresh KVCache: the whole prompt) or one decode step (one token per
+        row) of generation: the fused residual + norm chain of ``forward`` with the layers' cached attention."""
+        B, T = input_ids.shape
+        cache.begin(B, T)
+        x = self.embed_tokens(input_ids)
+        cos, sin = self.rotary.tables(cache.max_len, x.device, x.dtype)
+        first = self.layers[0].input_layernorm
+        h = fused.norm(x, first.weight, None, first.eps, rms=True)
+        for i, layer in enumerate(self.layers):
+            pn = layer.post_attention_layernorm
+            x, h = fused.dropout_add_norm(layer.self_attn(h, cos, sin, None, cache), x, pn.weight, None, pn.eps, 0.0,
+                                          rms=True)
+            nxt = self.layers[i + 1].input_layernorm if i + 1 < len(self.layers) else self.norm
+            x, h = fused.dropout_add_norm(layer.mlp(h), x, nxt.weight, None, nxt.eps, 0.0, rms=True)
+        cache.advance(T)
+        return h
 
-class LlamaForCausalLM(LossOptionsMixin, PreTrainedModel):
+
+class LlamaForCausalLM(NativeGenerateMixin, LossOptionsMixin, PreTrainedModel):
     config_class = LlamaConfig
     base_model_prefix = "model"
     _tied_weights_keys = {"lm_head.weight": "model.embed_tokens.weight"}
@@ -357,10 +408,12 @@ class LlamaForCausalLM(LossOptionsMixin, PreTrainedModel):
         self.model.gradient_checkpointing = False
 
     def forward(self, input_ids=None, labels=None, attention_mask=None, num_items_in_batch=None,
-                return_dict: Optional[bool] = None, position_ids=None, predictions: bool = False, **kwargs):
+                return_dict: Optional[bool] = None, position_ids=None, predictions: bool = False, cache=None,
+                **kwargs):
         # position_ids is a named parameter: HF's remove_unused_columns keeps only
         # those.  They switch on document-isolated attention (LlamaModel.forward).
-        h = self.model(input_ids, position_ids)
+        # cache (models/generation.py KVCache): the prefill or one decode step of generation.
+        h = self.model(input_ids, position_ids, cache)
         if predictions:  # evaluation without logits: loss, top-1 token and label rank per position
             return scored_output(self, h, self.lm_head.weight, labels, num_items_in_batch)
         loss = logits = None

@@ -604,7 +604,7 @@ def mlp_gelu(x: torch.Tensor, w_fc: torch.Tensor, b_fc: torch.Tensor, w_proj: to
 # OR a bit into a per-device int32 flag, which check_index_errors() reads
 # once per optimizer step without stalling the stream (one step late) or, at
 # the end of a run, synchronously.
-_IDX_EMBED, _IDX_LABEL, _IDX_POS = 1, 2, 4
+_IDX_EMBED, _IDX_LABEL, _IDX_POS, _IDX_CACHE = 1, 2, 4, 8
 _IDX_FLAGS: dict = {}  # device -> [flag int32[1] (device), pinned host mirror, copy-done event]
 
 
@@ -625,6 +625,9 @@ def _index_error(code: int, where: str):
         msgs.append("a label is outside [0, vocab_size) and is not the ignore index -100")
     if code & _IDX_POS:
         msgs.append(_POS_MSG)
+    if code & _IDX_CACHE:
+        msgs.append("a decode step's position is outside the KV cache [0, max_len) -- the cache is shorter than "
+                    "prompt + new tokens")
     return ValueError(f"dlion ({where}): " + "; ".join(msgs))
 
 
@@ -1144,6 +1147,147 @@ def rope_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch
         return causal_attention_gqa(qk_norm_rope(q, q_gamma, eps, cos, sin), qk_norm_rope(k, k_gamma, eps, cos, sin),
                                     v, dropout_p, window, bounds)
     return causal_attention_gqa(rope(q, cos, sin), rope(k, cos, sin), v, dropout_p, window, bounds)
+
+
+# ------------------------------------------------- generation: cache append + decode attention
+# One new token per sequence against a token-major cache [B, Tmax, Hkv, D] (csrc/decode.hip).
+_DECODE_MAX_SPLITS = 64  # csrc/kernels.h kDecodeMaxSplits
+_DECODE_MIN_CHUNK = 256  # keys: below this a split's fixed cost (q load, LDS merge, partial) shows
+_DECODE_TARGET_BLOCKS = 512  # two blocks for each of the 256 CUs
+
+
+def decode_splits(B: int, Hkv: int, max_len: int, window: int = 0, splits=None):
+    """(splits, chunk) of the decode-attention grid: ``splits`` blocks of ``chunk`` keys per (kv head, row).
+    A host rule over B, Hkv, max_len and the window only -- never kv_len, which lives on the device.  The keys
+    a row attends span at most ``min(window, max_len)``; split s owns the keys ``[lo + s chunk, lo + (s + 1)
+    chunk)`` of the row's range ``[lo, len)``.  ``splits`` forces the count (tests)."""
+    span = int(window) if 0 < int(window) < max_len else int(max_len)
+    if splits is None:
+        want = -(-_DECODE_TARGET_BLOCKS // max(1, B * Hkv))
+        splits = min(want, _DECODE_MAX_SPLITS, -(-span // _DECODE_MIN_CHUNK))
+    splits = max(1, min(int(splits), _DECODE_MAX_SPLITS, span))
+    chunk = -(-span // splits)
+    return -(-span // chunk), chunk
+
+
+def _step_rows_ok(x: torch.Tensor) -> bool:
+    """[B, heads, D] with contiguous heads and a 16-byte aligned row stride (a column view of a fused
+    q|k|v projection output of one token per sequence)."""
+    B, Hx, D = x.shape
+    return (x.stride(2) == 1 and (Hx == 1 or x.stride(1) == D) and x.data_ptr() % 16 == 0
+            and (B == 1 or (x.stride(0) % 8 == 0 and x.stride(0) >= Hx * D)))
+
+
+def _cache_ok(c: torch.Tensor) -> bool:
+    B, Tmax, Hkv, D = c.shape
+    return (c.dtype == torch.bfloat16 and c.stride(3) == 1 and (Hkv == 1 or c.stride(2) == D)
+            and (Tmax == 1 or (c.stride(1) % 8 == 0 and c.stride(1) >= Hkv * D))
+            and (B == 1 or (c.stride(0) % 8 == 0 and c.stride(0) >= Tmax * c.stride(1))) and c.data_ptr() % 16 == 0)
+
+
+def _rope_rows(x: torch.Tensor, c: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
+    """rope_reference for x [B, heads, D] with one table row per sequence (c / s [B, D]): the same ATen chain."""
+    d2 = x.shape[-1] // 2
+    rot = torch.cat([-x[..., d2:], x[..., :d2]], dim=-1)
+    return x * c[:, None, :] + rot * s[:, None, :]
+
+
+def kv_append_reference(q, k, v, pos, cos, sin, q_gamma, k_gamma, eps, k_cache, v_cache) -> torch.Tensor:
+    """The PyTorch form of kv_append (same arguments): rope_reference / qk_norm_rope_reference at position
+    pos[b], then an indexed write of k and v into cache[b, pos[b]]."""
+    Tmax = k_cache.shape[1]
+    p = pos.long()
+    bad = ((p < 0) | (p >= Tmax)).any()
+    if p.is_cuda:
+        _index_flag(p.device).bitwise_or_(bad.to(torch.int32) * _IDX_CACHE)
+    elif bool(bad):
+        raise _index_error(_IDX_CACHE, "kv_append")
+    p = p.clamp(0, Tmax - 1)
+    if cos is not None:
+        c, s = cos[p], sin[p]
+        if q_gamma is not None:
+            def normed(x, gamma):
+                xf = x if x.dtype == torch.float64 else x.float()
+                return gamma * (xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps)).to(x.dtype)
+
+            q, k = normed(q, q_gamma), normed(k, k_gamma)
+        q, k = _rope_rows(q, c, s), _rope_rows(k, c, s)
+    rows = torch.arange(p.shape[0], device=p.device)
+    k_cache[rows, p] = k.to(k_cache.dtype)
+    v_cache[rows, p] = v.to(v_cache.dtype)
+    return q.contiguous()
+
+
+def kv_append(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pos: torch.Tensor, cos, sin, q_gamma, k_gamma,
+              eps: float, k_cache: torch.Tensor, v_cache: torch.Tensor) -> torch.Tensor:
+    """One decode step's q [B, H, D], k / v [B, Hkv, D] (column views of the fused q|k|v output are read in
+    place): returns rope(norm(q)) [B, H, D] and writes rope(norm(k)) and v to ``cache[b, pos[b]]`` of the
+    token-major caches [B, Tmax, Hkv, D].  ``pos`` int32 [B]; ``cos`` / ``sin`` [>= Tmax, D] or None (GPT-2: a
+    pure append); ``q_gamma`` / ``k_gamma`` [D] or None (Qwen3 gains, ``eps``).  A position outside
+    [0, Tmax) is clamped and raises through check_index_errors (on the CPU: at once).  The rotation and
+    the norm are bit for bit those of ``rope`` / ``qk_norm_rope`` at that position."""
+    if (cos is None) != (sin is None) or (q_gamma is None) != (k_gamma is None) or (q_gamma is not None and cos is None):
+        raise ValueError("kv_append: cos / sin and q_gamma / k_gamma come as pairs, gains only with tables")
+    D = q.shape[-1]
+    Tmax = k_cache.shape[1]
+    if (q.dtype == k.dtype == v.dtype == torch.bfloat16 and D in (64, 128) and q.is_cuda and pos.is_cuda
+            and pos.dtype == torch.int32 and _cache_ok(k_cache) and _cache_ok(v_cache)
+            and all(t is None or (t.dtype == torch.bfloat16 and t.shape[0] >= Tmax) for t in (cos, sin))
+            and (q_gamma is None or all(g.dtype == torch.bfloat16 and g.is_contiguous() and g.data_ptr() % 16 == 0
+                                        for g in (q_gamma, k_gamma)))
+            and _use_hip(q)):
+        q, k, v = (t if _step_rows_ok(t) else t.contiguous() for t in (q, k, v))
+        if cos is not None:
+            cos, sin = cos.contiguous(), sin.contiguous()
+        return hip.ops().kv_append(q, k, v, pos.contiguous(), cos, sin, q_gamma, k_gamma, float(eps), k_cache, v_cache,
+                                   _index_flag(q.device))
+    return kv_append_reference(q, k, v, pos, cos, sin, q_gamma, k_gamma, eps, k_cache, v_cache)
+
+
+def decode_attention_reference(q, k_cache, v_cache, kv_len, window: int = 0, max_len=None) -> torch.Tensor:
+    """The PyTorch form of decode_attention (same arguments): masked softmax attention of one query per
+    sequence in fp32 (fp64 inputs stay fp64).  Cache elements outside a row's key range are replaced by
+    zeros before they enter a product, so whatever they hold (NaN included) cannot reach the output."""
+    B, H, D = q.shape
+    Tmax, Hkv = k_cache.shape[1], k_cache.shape[2]
+    L = Tmax if max_len is None else max(1, min(int(max_len), Tmax))
+    n = kv_len.long().clamp(0, L)
+    j = torch.arange(L, device=q.device)
+    visible = j[None, :] < n[:, None]
+    if window:
+        visible = visible & (j[None, :] >= (n - int(window))[:, None])
+    ct = torch.float64 if q.dtype == torch.float64 else torch.float32
+    zero = torch.zeros((), dtype=ct, device=q.device)
+    kf = torch.where(visible[:, :, None, None], k_cache[:, :L].to(ct), zero)
+    vf = torch.where(visible[:, :, None, None], v_cache[:, :L].to(ct), zero)
+    qf = q.to(ct).reshape(B, Hkv, H // Hkv, D)
+    s = torch.einsum("bkgd,btkd->bkgt", qf, kf) * (1.0 / D ** 0.5)
+    s = s.masked_fill(~visible[:, None, None, :], float("-inf"))
+    P = torch.softmax(s, dim=-1)
+    P = torch.where((n > 0)[:, None, None, None], P, zero)  # a row without keys: zeros, not 0 / 0
+    return torch.einsum("bkgt,btkd->bkgd", P, vf).reshape(B, H * D).to(q.dtype)
+
+
+def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, kv_len: torch.Tensor,
+                     window: int = 0, max_len=None, splits=None) -> torch.Tensor:
+    """q [B, H, D] (one new query per sequence), caches [B, Tmax, Hkv, D], kv_len int32 [B] -> [B, H * D]:
+    row b attends the keys ``max(0, kv_len[b] - window) .. kv_len[b] - 1`` of its cache (``window`` 0: all of
+    them; ``kv_len[b] == 0``: a zero row).  ``max_len`` is a host bound on kv_len (prompt width plus steps
+    taken; default Tmax): it sizes the split grid without a device sync, and kv_len is clamped to it.
+    bf16 at head_dim 64 / 128 with H / Hkv in 1..8 runs csrc/decode.hip (split over the keys, fp32 partials,
+    a combine pass; no atomics); anything else the PyTorch form.  ``splits`` forces the split count."""
+    B, H, D = q.shape
+    Tmax, Hkv = k_cache.shape[1], k_cache.shape[2]
+    window = int(window or 0)
+    max_len = Tmax if max_len is None else max(1, min(int(max_len), Tmax))
+    if (q.dtype == torch.bfloat16 and D in (64, 128) and H % Hkv == 0 and 1 <= H // Hkv <= 8 and q.is_cuda
+            and kv_len.is_cuda and kv_len.dtype == torch.int32 and _cache_ok(k_cache) and _cache_ok(v_cache)
+            and B <= 65535 and _use_hip(q)):
+        if not _step_rows_ok(q):
+            q = q.contiguous()
+        s, chunk = decode_splits(B, Hkv, max_len, window, splits)
+        return hip.ops().decode_attention(q, k_cache, v_cache, kv_len.contiguous(), window, max_len, s, chunk)
+    return decode_attention_reference(q, k_cache, v_cache, kv_len, window, max_len)
 
 
 # ------------------------------------------------------------------- LoRA

@@ -1,0 +1,106 @@
+#!/usr/bin/env python
+"""Generate text with a native model: KV cache + the gfx950 decode-attention kernel.
+
+    python generate.py --model_name_or_path gpt2 --prompt "The quick brown fox" --max_new_tokens 32
+    python generate.py --model_name_or_path ./sft/final_merged_checkpoint --prompt_file prompts.txt --bf16 \\
+        --do_sample --temperature 0.8 --top_p 0.95 --seed 0
+    python generate.py --model_name_or_path llama-2-7b --adapter ./sft/final_checkpoint --prompt "..." --bf16
+
+``--model_name_or_path`` is a named size (random weights, no hub access) or a local HF directory
+(models/registry.py); ``--adapter`` a peft-format LoRA directory as sft_llama2.py writes it.  A directory without a
+tokenizer falls back to the byte tokenizer.  Prompts of different lengths run as one left-padded batch.  Prints
+the completions and tokens/s.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from distributed_lion_pytorch_amd.models.lora import load_adapter  # noqa: E402
+from distributed_lion_pytorch_amd.models.registry import build_model, load_config  # noqa: E402
+from distributed_lion_pytorch_amd.utils.data import load_tokenizer  # noqa: E402
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--model_name_or_path", required=True)
+    ap.add_argument("--adapter", default=None, help="peft-format LoRA directory (sft_llama2.py's final_checkpoint)")
+    ap.add_argument("--prompt", action="append", default=[], help="a prompt (repeatable)")
+    ap.add_argument("--prompt_file", default=None, help="one prompt per line")
+    ap.add_argument("--max_new_tokens", type=int, default=64)
+    ap.add_argument("--do_sample", action="store_true")
+    ap.add_argument("--temperature", type=float, default=1.0)
+    ap.add_argument("--top_k", type=int, default=0)
+    ap.add_argument("--top_p", type=float, default=1.0)
+    ap.add_argument("--seed", type=int, default=None)
+    ap.add_argument("--bf16", action="store_true")
+    ap.add_argument("--device", default=None, help="cuda / cpu (default: cuda when there is one)")
+    ap.add_argument("--config_overrides", default=None, help="e.g. n_layer=2,n_embd=128 for a named size")
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    prompts = list(a.prompt)
+    if a.prompt_file:
+        with open(a.prompt_file) as f:
+            prompts += [line.rstrip("\n") for line in f if line.strip()]
+    if not prompts:
+        raise SystemExit("generate.py: give --prompt or --prompt_file")
+    device = torch.device(a.device or ("cuda" if torch.cuda.is_available() else "cpu"))
+    config = load_config(a.model_name_or_path, a.config_overrides)
+    model = build_model(config, a.model_name_or_path, torch_dtype="bfloat16" if a.bf16 else None)
+    if a.adapter:
+        model = load_adapter(model, a.adapter)
+    if a.bf16:
+        model = model.to(torch.bfloat16)
+    model = model.to(device).eval()
+    tok = load_tokenizer(a.model_name_or_path)
+
+    rows = [tok.encode(p) or [getattr(tok, "bos_token_id", None) or 0] for p in prompts]
+    vocab = model.config.vocab_size
+    if max(max(r) for r in rows) >= vocab:
+        raise SystemExit(f"generate.py: the tokenizer produces ids beyond the model's vocabulary ({vocab})")
+    width = max(len(r) for r in rows)
+    pad = getattr(tok, "pad_token_id", None)
+    pad = pad if pad is not None and pad < vocab else 0
+    ids = torch.full((len(rows), width), pad, dtype=torch.long)
+    mask = torch.zeros(len(rows), width, dtype=torch.long)
+    for b, r in enumerate(rows):  # left-padded, HF's generation convention
+        ids[b, width - len(r):] = torch.tensor(r)
+        mask[b, width - len(r):] = 1
+    eos = getattr(tok, "eos_token_id", None)
+    eos = eos if eos is not None and eos < vocab else None
+    ids, mask = ids.to(device), mask.to(device)
+
+    def sync():
+        if device.type == "cuda":
+            torch.cuda.synchronize(device)
+
+    sync()
+    t0 = time.perf_counter()
+    out = model.generate(ids, attention_mask=mask, max_new_tokens=a.max_new_tokens, do_sample=a.do_sample,
+                         temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, eos_token_id=eos,
+                         pad_token_id=pad if eos is not None else None, seed=a.seed)
+    sync()
+    dt = time.perf_counter() - t0
+    new = out[:, width:].tolist()
+    n_tokens = 0
+    for p, r in zip(prompts, new):
+        if eos is not None and eos in r:
+            r = r[:r.index(eos)]
+        n_tokens += len(r)
+        print(f"--- {p!r}\n{tok.decode(r)}")
+    print(f"[generate] {len(prompts)} prompt(s), {out.shape[1] - width} steps, {n_tokens} new tokens in {dt:.3f} s: "
+          f"{n_tokens / dt:.1f} tokens/s on {device}")
+    return out
+
+
+if __name__ == "__main__":
+    main()
