@@ -1453,9 +1453,82 @@ Tensor decode_attention(const Tensor& q, const Tensor& k_cache, const Tensor& v_
             "decode_attention");
   return out;
 }
+// ---- decode projections (csrc/skinny_gemm.hip)
+// the operands both forms share: x [M, K] bf16 rows (unit inner stride, 16-byte aligned base and row stride), out a
+// row-major bf16 [M, N] view with its own leading dimension, bias contiguous bf16 [N]; (splits, per) from
+// ops/fused.py skinny_splits.  Returns the fp32 partials buffer (undefined for one split).
+Tensor check_skinny(const char* what, const Tensor& x, int64_t N, const std::optional<Tensor>& bias, const Tensor& out,
+                    int64_t splits, int64_t per) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.scalar_type() == at::kBFloat16, "dlion ", what, ": x must be a bf16 [M, K] GPU tensor");
+  const int64_t M = x.size(0), K = x.size(1);
+  TORCH_CHECK(M >= 1 && M <= dlion::kSkinnyMaxM, "dlion ", what, ": M must be in [1, 16], got ", M);
+  TORCH_CHECK(K >= 64 && K % 64 == 0 && K < (int64_t{1} << 31), "dlion ", what, ": K must be a positive multiple of 64, got ", K);
+  TORCH_CHECK(N >= 1 && N < (int64_t{1} << 31), "dlion ", what, ": bad N ", N);
+  TORCH_CHECK(x.stride(1) == 1 && (M == 1 || (x.stride(0) % 8 == 0 && x.stride(0) >= K)) &&
+                  reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "dlion ", what, ": x needs unit inner stride, a row stride % 8 == 0 and a 16-byte aligned base");
+  TORCH_CHECK(out.is_cuda() && out.dim() == 2 && out.scalar_type() == at::kBFloat16 && out.size(0) == M &&
+                  out.size(1) == N && out.stride(1) == 1 && (M == 1 || out.stride(0) >= N) && out.device() == x.device(),
+              "dlion ", what, ": out must be a row-major bf16 [M, N] view on x's device");
+  if (bias.has_value())
+    TORCH_CHECK(bias->is_cuda() && bias->scalar_type() == at::kBFloat16 && bias->is_contiguous() && bias->numel() == N &&
+                    bias->device() == x.device(),
+                "dlion ", what, ": bias must be a contiguous bf16 [N] tensor on x's device");
+  const int64_t steps = (K + 127) / 128;
+  TORCH_CHECK(splits >= 1 && splits <= dlion::kSkinnyMaxSplits && per >= 1 && (splits - 1) * per < steps &&
+                  splits * per >= steps,
+              "dlion ", what, ": bad splits / steps per split (", splits, ", ", per, ") for ", steps, " steps");
+  return splits > 1 ? at::empty({splits, M, N}, x.options().dtype(at::kFloat)) : Tensor();
+}
+
+void skinny_gemm_nt(const Tensor& x, const Tensor& w, const std::optional<Tensor>& bias, const Tensor& out,
+                    int64_t splits, int64_t per) {
+  TORCH_CHECK(w.is_cuda() && w.dim() == 2 && w.scalar_type() == at::kBFloat16 && w.is_contiguous() &&
+                  reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0 && x.dim() == 2 && w.size(1) == x.size(1) &&
+                  w.device() == x.device(),
+              "dlion skinny_gemm_nt: w must be a contiguous, 16-byte aligned bf16 [N, K] tensor on x's device");
+  const int64_t N = w.size(0);
+  const c10::DeviceGuard dg(x.device());
+  Tensor part = check_skinny("skinny_gemm_nt", x, N, bias, out, splits, per);
+  const int64_t M = x.size(0), K = x.size(1);
+  check_hip(dlion::launch_skinny_gemm_nt(x.data_ptr(), M == 1 ? K : x.stride(0), w.data_ptr(),
+                                         bias.has_value() ? bias->data_ptr() : nullptr, out.data_ptr(),
+                                         M == 1 ? N : out.stride(0), part.defined() ? part.data_ptr<float>() : nullptr,
+                                         static_cast<int>(M), static_cast<int>(N), static_cast<int>(K),
+                                         static_cast<int>(splits), static_cast<int>(per), cur_stream()),
+            "skinny_gemm_nt");
+}
+
+void skinny_gemm_w4(const Tensor& x, const Tensor& qweight, const Tensor& absmax, const Tensor& code, int64_t N,
+                    const std::optional<Tensor>& bias, const Tensor& out, int64_t splits, int64_t per) {
+  check_dev(qweight, "qweight");
+  check_dev(absmax, "absmax");
+  check_dev(code, "code");
+  TORCH_CHECK(x.dim() == 2 && N >= 1, "dlion skinny_gemm_w4: x must be [M, K], N positive");
+  const int64_t K = x.size(1);
+  TORCH_CHECK(qweight.scalar_type() == at::kByte && qweight.numel() * 2 == N * K && absmax.scalar_type() == at::kFloat &&
+                  absmax.numel() * 64 == N * K && code.scalar_type() == at::kFloat && code.numel() == 16 &&
+                  reinterpret_cast<uintptr_t>(qweight.data_ptr()) % 16 == 0 && qweight.device() == x.device() &&
+                  absmax.device() == x.device() && code.device() == x.device(),
+              "dlion skinny_gemm_w4: qweight (uint8, 16-byte aligned) / absmax (fp32 per 64) / code (fp32[16]) do not "
+              "match an [N, K] weight on x's device");
+  const c10::DeviceGuard dg(x.device());
+  Tensor part = check_skinny("skinny_gemm_w4", x, N, bias, out, splits, per);
+  const int64_t M = x.size(0);
+  check_hip(dlion::launch_skinny_gemm_w4(x.data_ptr(), M == 1 ? K : x.stride(0), qweight.data_ptr<uint8_t>(),
+                                         absmax.data_ptr<float>(), code.data_ptr<float>(),
+                                         bias.has_value() ? bias->data_ptr() : nullptr, out.data_ptr(),
+                                         M == 1 ? N : out.stride(0), part.defined() ? part.data_ptr<float>() : nullptr,
+                                         static_cast<int>(M), static_cast<int>(N), static_cast<int>(K),
+                                         static_cast<int>(splits), static_cast<int>(per), cur_stream()),
+            "skinny_gemm_w4");
+}
 }  // namespace
 
 TORCH_LIBRARY(dlion, m) {
+  m.def("skinny_gemm_nt(Tensor x, Tensor w, Tensor? bias, Tensor(a!) out, int splits, int per) -> ()");
+  m.def("skinny_gemm_w4(Tensor x, Tensor qweight, Tensor absmax, Tensor code, int N, Tensor? bias, Tensor(a!) out,"
+        " int splits, int per) -> ()");
   m.def("dequant4_t_(Tensor q, Tensor absmax, Tensor code, Tensor(a!) out) -> ()");
   m.def("transpose_pad(Tensor x, int rows_out=-1) -> Tensor");
   m.def("kv_append(Tensor q, Tensor k, Tensor v, Tensor pos, Tensor? cos, Tensor? sin, Tensor? q_gamma, Tensor? k_gamma,"
@@ -1598,4 +1671,6 @@ TORCH_LIBRARY_IMPL(dlion, CUDA, m) {
   m.impl("transpose_pad", &transpose_pad);
   m.impl("kv_append", &kv_append);
   m.impl("decode_attention", &decode_attention);
+  m.impl("skinny_gemm_nt", &skinny_gemm_nt);
+  m.impl("skinny_gemm_w4", &skinny_gemm_w4);
 }

@@ -195,4 +195,18 @@ hipError_t launch_decode_attention(const void* q, int64_t q_ld, const void* k_ca
                                    float* part_l, float* part_o, void* out, int B, int H, int Hkv, int D, int Tmax,
                                    int max_len, int window, int splits, int chunk, float scale, hipStream_t st);
 
+// ---- decode projections (skinny_gemm.hip); bf16, 1 <= M <= 16, K % 64 == 0, any N
+// out[M, N] (row stride ldo) = x[M, K] (row stride ldx, 16-byte aligned rows) . w[N, K]^T (+ bias[N]), fp32
+// accumulation, one rounding.  The 128-k steps of K are cut into `splits` runs of `per` steps ((splits - 1) per <
+// steps <= splits per); splits > 1 needs part, fp32 [splits, M, N], and runs the combine pass.  The weight is
+// contiguous bf16 [N, K], or quant.hip's 4-bit store of it (q, absmax per 64 elements, a 16-entry code); the
+// two forms give the same bits for the same weight values.
+constexpr int kSkinnyMaxM = 16;
+constexpr int kSkinnyMaxSplits = 32;
+hipError_t launch_skinny_gemm_nt(const void* x, int64_t ldx, const void* w, const void* bias, void* out, int64_t ldo,
+                                 float* part, int M, int N, int K, int splits, int per, hipStream_t st);
+hipError_t launch_skinny_gemm_w4(const void* x, int64_t ldx, const uint8_t* q, const float* absmax, const float* code,
+                                 const void* bias, void* out, int64_t ldo, float* part, int M, int N, int K,
+                                 int splits, int per, hipStream_t st);
+
 }  // namespace dlion

@@ -16,9 +16,9 @@ from __future__ import annotations
 from typing import Optional
 
 import torch
-import torch.nn.functional as F
 
 from ..ops import fused
+from ..ops.linear import gemm_fwd
 
 _EOS_CHECK_EVERY = 8  # decode steps between two host reads of "every row has finished"
 
@@ -184,7 +184,7 @@ class NativeGenerateMixin:
         ignore = torch.full((B,), -100, dtype=torch.long, device=dev)
         for i in range(max_new_tokens):
             if do_sample:
-                logits = warp_logits(F.linear(h, weight), temperature, top_k, top_p)
+                logits = warp_logits(gemm_fwd(h, weight), temperature, top_k, top_p)
                 tok = torch.multinomial(logits.softmax(-1), 1, generator=gen)[:, 0]
             else:
                 tok = fused.lm_head_score(h, weight, ignore).pred.long()

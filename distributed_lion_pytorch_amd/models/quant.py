@@ -23,7 +23,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ..ops.linear import _adjacent_views, autocast_inputs, gemm_fwd
+from ..ops.linear import _Fn, _adjacent_views, autocast_inputs, gemm_fwd, skinny_shape_ok
 from ..ops.quant import BLOCK, code_tensor, dequantize_4bit, quantize_4bit
 
 
@@ -142,7 +142,7 @@ def _dequant_cat_t(layers, dtype, device) -> torch.Tensor:
     return Wt
 
 
-class _Linear4bitMulti(torch.autograd.Function):
+class _Linear4bitMulti(_Fn):
     """[y1 | y2 | ...] = x @ [W1; W2; ...]^T (+ b for one layer) with the 4-bit
     weights expanded into one transient buffer; backward re-expands it for
     dx = dy @ W (the frozen weights get no gradient; nothing but the layer
@@ -179,9 +179,37 @@ class _Linear4bitMulti(torch.autograd.Function):
         return (dx, db) + (None,) * len(ctx.layers)
 
 
+def _skinny_w4_route(x2d: torch.Tensor, layers, bias) -> bool:
+    """A decode step (inference, at most 16 bf16 rows on the GPU): multiply straight from the 4-bit store
+    (ops/fused.py skinny_gemm_w4) instead of expanding every weight around its GEMM.  Static, like
+    ops/linear.py skinny_route."""
+    from ..ops import hip, linear
+
+    M, K = x2d.shape
+    return (linear._decode_rows(x2d) and linear.skinny_rows_ok(x2d)
+            and all(l.in_features == K and skinny_shape_ok(M, l.out_features, K) and l.qweight.is_cuda
+                    and l.qweight.data_ptr() % 16 == 0 for l in layers)
+            and (bias is None or (bias.dtype == torch.bfloat16 and bias.is_contiguous())) and hip.available())
+
+
+def _skinny_w4_multi(x2d: torch.Tensor, layers, bias) -> tuple:
+    """One skinny_gemm_w4 launch per layer, each into its column block of one [M, sum N] buffer (the layout
+    the expansion path's single GEMM returns); nothing is expanded."""
+    from ..ops import fused
+
+    sizes = [l.out_features for l in layers]
+    y = torch.empty(x2d.shape[0], sum(sizes), dtype=x2d.dtype, device=x2d.device)
+    outs = y.split(sizes, dim=-1)
+    for l, o in zip(layers, outs):
+        fused.skinny_gemm_w4(x2d, l.qweight, l.absmax, l.quant_map, l.out_features, bias, out=o)
+    return outs
+
+
 def linear4bit_multi(x: torch.Tensor, layers: Sequence[Linear4bit], bias: Optional[torch.Tensor] = None) -> tuple:
     """(x @ W1^T, x @ W2^T, ...) for 4-bit layers sharing the input x, as one
-    GEMM on the concatenated expanded weights; ``bias`` only with one layer."""
+    GEMM on the concatenated expanded weights; ``bias`` only with one layer.
+    A decode step (no gradients, at most 16 rows on the GPU) expands nothing:
+    one weight-streaming launch per layer reads the 4-bit store itself."""
     assert bias is None or len(layers) == 1
     lead = x.shape[:-1]
     x2d = x.reshape(-1, x.shape[-1])
@@ -190,7 +218,11 @@ def linear4bit_multi(x: torch.Tensor, layers: Sequence[Linear4bit], bias: Option
     if x.is_cuda:
         x2d, bias = autocast_inputs(x2d, bias)
         with torch.autocast("cuda", enabled=False):
-            outs = _Linear4bitMulti.apply(x2d, bias if bias is None else bias.to(x2d.dtype), *layers)
+            bias = bias if bias is None else bias.to(x2d.dtype)
+            if _skinny_w4_route(x2d, layers, bias):
+                outs = _skinny_w4_multi(x2d, layers, bias)
+            else:
+                outs = _Linear4bitMulti.apply(x2d, bias, *layers)
     else:
         outs = _Linear4bitMulti.apply(x2d, bias if bias is None else bias.to(x2d.dtype), *layers)
     return tuple(o.view(lead + (o.shape[-1],)) for o in outs)

@@ -19,7 +19,7 @@ import torch
 import torch.nn.functional as F
 
 from . import hip
-from .linear import gemm_fwd
+from .linear import _Fn, gemm_fwd
 
 _IMPL = {"mode": "auto"}  # auto | torch | hip (set_impl)
 
@@ -501,7 +501,7 @@ def _own_gemm_ok(a: torch.Tensor, b_nk: torch.Tensor) -> bool:
             and a.data_ptr() % 16 == 0 and a.shape[0] * a.stride(0) < 2 ** 31)
 
 
-class _MLP(torch.autograd.Function):
+class _MLP(_Fn):
     """y = gelu(x @ Wfc + b) @ Wproj for the GPT-2 MLP (both weights in HF
     Conv1D [in, out] layout, no output bias: the caller's residual+norm kernel
     adds it).  Measured at the bench shape (20480 tokens, C 768, 4C 3072;
@@ -887,7 +887,7 @@ def causal_attention(qkv: torch.Tensor, dropout_p: float) -> torch.Tensor:
     return y.transpose(1, 2).reshape(B, T, H * D)
 
 
-class _QKVAttention(torch.autograd.Function):
+class _QKVAttention(_Fn):
     """y = causal_attention(x @ Wqkv + b) for GPT-2's packed c_attn projection
     (Wqkv in HF Conv1D [C, 3C] layout).  One op so that the backward can take
     the c_attn bias gradient from the attention kernels themselves: the dQ /
@@ -1290,6 +1290,98 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
     return decode_attention_reference(q, k_cache, v_cache, kv_len, window, max_len)
 
 
+# ------------------------------------------------- generation: the M <= 16 projections (csrc/skinny_gemm.hip)
+_SKINNY_STEP = 128  # k of one step of the kernel: the unit K is split in
+_SKINNY_CHUNK = 4  # steps a wave loads together: runs are whole chunks where K allows
+_SKINNY_MAX_SPLITS = 32  # csrc/kernels.h kSkinnyMaxSplits
+_SKINNY_TARGET_BLOCKS = 512  # two blocks (8 waves, 20 KB of weight loads in flight each) for each of the 256 CUs
+_SKINNY_TALL_N = 4096  # csrc/skinny_gemm.hip kTallMaxN: an unsplit launch at N <= this splits K over a block's waves
+_SKINNY_TALL_ELEMS = 8 << 20  # weights up to this many elements (16 MB of bf16) are not split over blocks
+
+
+def skinny_splits(M: int, N: int, K: int, splits=None):
+    """(splits, steps per split) of the skinny GEMM's grid: the ceil(K / 128) steps of the reduction are cut
+    into ``splits`` runs over blocks, every one non-empty.  A pure host rule over the shape.  Small weights
+    (N <= 4096 and N K <= 8 Mi elements: GPT-2's and Qwen2-0.5B's projections) take one run: the kernel then
+    splits K over the 4 waves of a block (16 weight rows per block, the tiles added through LDS), one launch,
+    no partials.  Otherwise N is split first (64 weight rows per block) and K only while N / 64 blocks leave
+    CUs without two blocks, in runs of whole 4-step chunks, which cost a partials buffer and the combine pass.
+    ``splits`` forces the count (tests); it is clamped to [1, min(32, steps)] and lowered to the count that
+    leaves no split empty.  M does not enter: the M rows ride in one MFMA tile."""
+    steps = -(-int(K) // _SKINNY_STEP)
+    forced = splits is not None
+    if not forced:
+        if N <= _SKINNY_TALL_N and N * K <= _SKINNY_TALL_ELEMS:
+            return 1, steps
+        want = -(-_SKINNY_TARGET_BLOCKS // -(-int(N) // 64))
+        splits = min(want, max(1, steps // _SKINNY_CHUNK))
+    splits = max(1, min(int(splits), _SKINNY_MAX_SPLITS, steps))
+    per = -(-steps // splits)
+    if not forced and _SKINNY_CHUNK < per < steps:
+        per = -(-per // _SKINNY_CHUNK) * _SKINNY_CHUNK  # no half-used chunk but a run's last
+    return -(-steps // per), per
+
+
+def skinny_gemm_reference(x: torch.Tensor, w: torch.Tensor, bias=None) -> torch.Tensor:
+    """The PyTorch form of skinny_gemm: ``F.linear``."""
+    return F.linear(x, w, bias)
+
+
+def skinny_gemm_w4_reference(x: torch.Tensor, qweight: torch.Tensor, absmax: torch.Tensor, code: torch.Tensor,
+                             N: int, bias=None) -> torch.Tensor:
+    """The PyTorch form of skinny_gemm_w4: ``F.linear`` on the dequantised weight (ops/quant.py)."""
+    from .quant import dequantize_4bit
+
+    return F.linear(x, dequantize_4bit(qweight, absmax, code, (int(N), x.shape[-1]), x.dtype), bias)
+
+
+def _skinny_out(x: torch.Tensor, N: int, out):
+    if out is None:
+        return torch.empty(x.shape[0], N, dtype=x.dtype, device=x.device)
+    if tuple(out.shape) != (x.shape[0], N) or out.dtype != x.dtype or out.device != x.device:
+        raise ValueError(f"skinny_gemm: out must be a {x.dtype} [{x.shape[0]}, {N}] tensor on {x.device}")
+    return out
+
+
+def skinny_gemm(x: torch.Tensor, w: torch.Tensor, bias=None, out=None, splits=None) -> torch.Tensor:
+    """x [M, K] @ w [N, K]^T (+ bias [N]) for the 1 <= M <= 16 rows of a decode step: bf16, fp32 accumulation,
+    one rounding.  On the GPU csrc/skinny_gemm.hip streams the weight once (16-byte loads straight to
+    registers, 16 x 16 x 32 MFMAs with the rows padded by zero fragments); operands it does not take
+    (``linear.skinny_eligible``) raise -- callers route by that predicate.  ``out``: a row-major [M, N] view with
+    its own leading dimension (a column block of a wider buffer).  ``splits`` forces the K split count; every
+    count gives the same bits for sums that are exact in fp32, and a fixed count always the same bits.  Off the
+    GPU: ``F.linear``."""
+    if x.dim() != 2 or w.dim() != 2 or x.shape[1] != w.shape[1]:
+        raise ValueError(f"skinny_gemm: x [M, K] and w [N, K] expected, got {tuple(x.shape)} and {tuple(w.shape)}")
+    N = w.shape[0]
+    out = _skinny_out(x, N, out)
+    if _use_hip(x):
+        s, per = skinny_splits(x.shape[0], N, x.shape[1], splits)
+        hip.ops().skinny_gemm_nt(x, w, bias, out, s, per)
+        return out
+    out.copy_(skinny_gemm_reference(x, w, bias))
+    return out
+
+
+def skinny_gemm_w4(x: torch.Tensor, qweight: torch.Tensor, absmax: torch.Tensor, code: torch.Tensor, N: int,
+                   bias=None, out=None, splits=None) -> torch.Tensor:
+    """skinny_gemm against a weight [N, K] kept in the 4-bit block store (ops/quant.py: ``qweight`` two indices
+    per byte, high nibble first; fp32 ``absmax`` per 64 elements; the 16-entry fp32 ``code``), multiplied straight
+    from that store: 0.56 bytes per weight element are read and nothing is expanded in memory.  The weight value
+    is ``bf16(code[idx] * absmax)``, the bits ``dequantize_4bit`` writes, and the product is taken exactly as
+    skinny_gemm takes it: the result equals ``skinny_gemm(x, dequantize_4bit(...))`` bit for bit."""
+    if x.dim() != 2 or 2 * qweight.numel() != int(N) * x.shape[1]:
+        raise ValueError(f"skinny_gemm_w4: x {tuple(x.shape)} and {qweight.numel()} packed bytes do not make an "
+                         f"[{N}, K] weight")
+    out = _skinny_out(x, int(N), out)
+    if _use_hip(x):
+        s, per = skinny_splits(x.shape[0], int(N), x.shape[1], splits)
+        hip.ops().skinny_gemm_w4(x, qweight, absmax, code, int(N), bias, out, s, per)
+        return out
+    out.copy_(skinny_gemm_w4_reference(x, qweight, absmax, code, N, bias))
+    return out
+
+
 # ------------------------------------------------------------------- LoRA
 def _lora_rows_ok(t: torch.Tensor) -> bool:
     return (t.dim() == 2 and t.dtype == torch.bfloat16 and t.stride(1) == 1 and t.stride(0) % 8 == 0
@@ -1518,7 +1610,7 @@ def _lm_wgrad_partials(g: torch.Tensor, h2d: torch.Tensor, v: int):
     return part.view(s, -1)[:, : v * h2d.shape[1]]
 
 
-class _LMHeadCE(torch.autograd.Function):
+class _LMHeadCE(_Fn):
     """loss = mean_{labels != -100} CE(h @ W^T, labels), gradients computed in
     the forward pass (the loss gradient is a scalar multiple of
     softmax - onehot), so the [N, V] logits never persist and never exist in
@@ -1744,7 +1836,7 @@ def _softmax_xent_torch_(logits: torch.Tensor, labels: torch.Tensor, v: int, lab
     return row_loss
 
 
-class _TokenLogp(torch.autograd.Function):
+class _TokenLogp(_Fn):
     """Per-token log p(label) of ``h @ W^T`` (0 for labels == -100) through the
     same fused softmax-xent kernel: the [N, V] logits are turned into
     softmax - onehot in place; forward-only callers (the frozen DPO reference

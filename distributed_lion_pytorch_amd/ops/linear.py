@@ -58,6 +58,7 @@ from __future__ import annotations
 import contextlib
 import math
 import os
+import threading
 import weakref
 
 import torch
@@ -874,12 +875,124 @@ def _tunable(a: torch.Tensor, M: int, N: int, K: int) -> bool:
             and not torch.cuda.is_current_stream_capturing() and hip.available())
 
 
+# ------------------------------------------------ decode projections (M <= 16 rows)
+# A decode step's GEMMs have one row per sequence: they stream the weight once and are bound by that stream,
+# which hipBLASLt's 16-row tiles serve badly (docs/DESIGN.md "Skinny-M GEMM for decode").  Without gradients,
+# gemm_fwd hands eligible operands to csrc/skinny_gemm.hip.  The rule is static -- shapes, strides, dtypes,
+# alignment and the grad mode, no timing -- so the path can be captured in a graph later.
+_SKINNY = os.environ.get("DLION_SKINNY_GEMM", "1") != "0"
+SKINNY_MAX_M = 16  # csrc/kernels.h kSkinnyMaxM
+_FN_DEPTH = threading.local()
+
+
+class _Fn(torch.autograd.Function):
+    """autograd.Function that counts its running forwards: the base of every Function of this package whose
+    body runs a GEMM (gemm_fwd or a linear wrapper).  Autograd runs a Function's forward and backward with
+    grad mode off whatever the caller's mode was, so ``torch.is_grad_enabled()`` read in there says nothing
+    about training; :func:`inference_call` looks at this count (forward) and at the engine's current node
+    (backward) as well."""
+
+    @classmethod
+    def apply(cls, *args, **kwargs):
+        _FN_DEPTH.n = getattr(_FN_DEPTH, "n", 0) + 1
+        try:
+            return super().apply(*args, **kwargs)
+        finally:
+            _FN_DEPTH.n -= 1
+
+
+def inference_call() -> bool:
+    """No gradient is being recorded and the caller is not inside the forward of an ``_Fn`` or inside any
+    backward: what runs now is inference, not a piece of a training step."""
+    return (not torch.is_grad_enabled() and getattr(_FN_DEPTH, "n", 0) == 0
+            and torch._C._current_autograd_node() is None)
+
+
+def skinny_shape_ok(M: int, N: int, K: int) -> bool:
+    """Shapes csrc/skinny_gemm.hip takes: 1 <= M <= 16 rows, K a multiple of 64 (a 4-bit block never straddles
+    two weight rows), any N."""
+    return 1 <= M <= SKINNY_MAX_M and N >= 1 and K >= 64 and K % 64 == 0 and N < 2 ** 31 and K < 2 ** 31
+
+
+def skinny_rows_ok(x2d: torch.Tensor) -> bool:
+    """x [M, K] as the kernels read it: unit inner stride, a row stride that is a multiple of 8 elements and a
+    16-byte aligned base."""
+    M, K = x2d.shape
+    return (x2d.stride(1) == 1 and (M == 1 or (x2d.stride(0) % 8 == 0 and x2d.stride(0) >= K))
+            and x2d.data_ptr() % 16 == 0)
+
+
+def skinny_eligible(x2d: torch.Tensor, w: torch.Tensor, bias=None) -> bool:
+    """Would ``fused.skinny_gemm(x2d, w, bias)`` take these operands?  A pure host predicate over shapes,
+    strides, dtypes and alignment (the device is the caller's business, so it can be asked of CPU tensors):
+    bf16 throughout; x2d [M, K] with unit inner stride, a row stride that is a multiple of 8 and a 16-byte
+    aligned base; w [N, K] contiguous and 16-byte aligned; bias contiguous [N]."""
+    if not (x2d.dim() == 2 and w.dim() == 2 and x2d.dtype == w.dtype == torch.bfloat16 and x2d.shape[1] == w.shape[1]
+            and x2d.device == w.device):
+        return False
+    M, K = x2d.shape
+    N = w.shape[0]
+    if not skinny_shape_ok(M, N, K):
+        return False
+    if bias is not None and not (bias.dtype == torch.bfloat16 and bias.dim() == 1 and bias.shape[0] == N
+                                 and bias.is_contiguous() and bias.device == w.device):
+        return False
+    return skinny_rows_ok(x2d) and w.is_contiguous() and w.data_ptr() % 16 == 0
+
+
+# Shape classes of the bf16 rule, by kernel time (profiles/r13/decode.txt, docs/DESIGN.md): a class is routed only
+# where csrc/skinny_gemm.hip measured faster than hipBLASLt's kernel on the same operands.
+#   N K <= 16 Mi elements (GPT-2's and Qwen2-0.5B's projections, 4096 x 4096)   1.18 - 1.67 x faster  routed
+#   16 Mi < N K < 64 Mi (Llama-3-8B q|k|v 6144 x 4096: 16.0-17.5 against 14.8 us)                      hipBLASLt
+#   N K >= 64 Mi with N <= 32768 and K <= 8192 (gate|up 28672 x 4096)           1.08 - 1.18 x faster  routed
+#   N > 32768 (LM heads: 128256 x 4096 0.93-0.95 x, 50257 x 768 0.77-0.92 x)                           hipBLASLt
+#   K > 8192 (down_proj 4096 x 14336: K split over blocks plus the combine pass, 0.83-0.87 x)          hipBLASLt
+# The 4-bit form is 1.5-4.4 x faster than expansion + GEMM in every class and is not narrowed.
+SKINNY_MAX_N = 32768
+SKINNY_MAX_K = 8192
+SKINNY_SMALL_ELEMS = 16 << 20
+SKINNY_LARGE_ELEMS = 64 << 20
+
+
+def skinny_routed_shape(M: int, N: int, K: int) -> bool:
+    """skinny_shape_ok minus the classes where hipBLASLt's kernel measured faster (see above)."""
+    return (skinny_shape_ok(M, N, K) and N <= SKINNY_MAX_N and K <= SKINNY_MAX_K
+            and (N * K <= SKINNY_SMALL_ELEMS or N * K >= SKINNY_LARGE_ELEMS))
+
+
+def skinny_route(x2d: torch.Tensor, w: torch.Tensor, bias=None) -> bool:
+    """gemm_fwd's rule for the skinny kernel: inference (inference_call), GPU operands that are eligible and of
+    a routed shape class, and ``DLION_SKINNY_GEMM`` not 0."""
+    from . import hip
+
+    return (_SKINNY and x2d.is_cuda and x2d.dim() == 2 and w.dim() == 2 and x2d.shape[0] <= SKINNY_MAX_M
+            and inference_call() and skinny_routed_shape(x2d.shape[0], w.shape[0], x2d.shape[1])
+            and skinny_eligible(x2d, w, bias) and hip.available())
+
+
+def _decode_rows(x2d: torch.Tensor) -> bool:
+    """The cheap part of skinny_route, asked before a wrapper builds a derived weight for it."""
+    return _SKINNY and x2d.is_cuda and x2d.shape[0] <= SKINNY_MAX_M and x2d.dtype == torch.bfloat16 and inference_call()
+
+
+def _skinny(x2d: torch.Tensor, w: torch.Tensor, bias=None) -> torch.Tensor:
+    from . import fused
+
+    return fused.skinny_gemm(x2d, w, bias)
+
+
+# NOTE for new autograd Functions: a Function whose forward or backward calls gemm_fwd (or a linear wrapper) must
+# derive from _Fn, or a training step with M <= 16 rows would take the inference kernel from inside it
+# (tests/test_skinny_gemm_cpu.py walks the package and checks this).
 def gemm_fwd(x2d: torch.Tensor, w: torch.Tensor, bias=None) -> torch.Tensor:
     """x2d @ w^T (+ bias) (w [N, K], nn.Linear layout; also any NT product,
     e.g. an HF Conv1D input gradient dy @ W^T): ATen, or the measured-fastest of
-    ATen / own NT / tuned hipBLASLt for large bf16 shapes."""
+    ATen / own NT / tuned hipBLASLt for large bf16 shapes; a decode step's
+    M <= 16 rows without gradients go to the skinny kernel (skinny_route)."""
     M, K = x2d.shape
     N = w.shape[0]
+    if skinny_route(x2d, w, bias):
+        return _skinny(x2d, w, bias)
     if not (_tunable(x2d, M, N, K) and w.dtype == torch.bfloat16 and w.dim() == 2):
         return torch.nn.functional.linear(x2d, w, bias)
     cands = _nt_candidates(x2d, w, "", bias)
@@ -937,7 +1050,7 @@ def gemm_dgrad(dy: torch.Tensor, w: torch.Tensor, frozen: bool) -> torch.Tensor:
     return _nt_candidates(dy, wt, "nt_")[name]()
 
 
-class _LinearKN(torch.autograd.Function):
+class _LinearKN(_Fn):
     """y = x @ W + b with W stored [K, N] (HF Conv1D layout)."""
 
     @staticmethod
@@ -967,7 +1080,7 @@ class _LinearKN(torch.autograd.Function):
         return dx, dw, db
 
 
-class _LinearNK(torch.autograd.Function):
+class _LinearNK(_Fn):
     """y = x @ W^T + b with W stored [N, K] (nn.Linear layout)."""
 
     @staticmethod
@@ -1072,7 +1185,7 @@ def _adjacent_views(ts):
     return t0.as_strided(t0.shape[:-1] + (n,), t0.stride())
 
 
-class _LinearMultiNK(torch.autograd.Function):
+class _LinearMultiNK(_Fn):
     """[y1 | y2 | ...] = x @ [W1; W2; ...]^T as ONE GEMM for projections that
     share their input (Llama q/k/v, gate/up); the outputs are column views of
     the fused result.  Backward: one input-gradient GEMM on the concatenated
@@ -1232,7 +1345,12 @@ def linear_multi_nk(x: torch.Tensor, ws) -> tuple:
     pack_projections(ws)
     x2d, *ws = autocast_inputs(x2d, *ws)
     with torch.autocast("cuda", enabled=False):
-        outs = _LinearMultiNK.apply(x2d, *ws)
+        wc = cat_weights(ws) if _decode_rows(x2d) else None
+        if wc is not None and skinny_route(x2d, wc):
+            # a decode step: one skinny GEMM on the cached concatenated weight, no autograd node
+            outs = _skinny(x2d, wc).split([w.shape[0] for w in ws], dim=-1)
+        else:
+            outs = _LinearMultiNK.apply(x2d, *ws)
     return tuple(o.view(lead + (o.shape[-1],)) for o in outs)
 
 
@@ -1255,7 +1373,12 @@ def linear_kn(x: torch.Tensor, w: torch.Tensor, b=None) -> torch.Tensor:
     else:
         x2d, w, b = autocast_inputs(x2d, w, b)
         with torch.autocast("cuda", enabled=False):
-            y = _LinearKN.apply(x2d, w, b)
+            # a decode step: the skinny GEMM against the cached W^T (the layout _LinearKN.forward uses too)
+            wt = transposed_weight(w) if _decode_rows(x2d) and isinstance(w, torch.nn.Parameter) else None
+            if wt is not None and skinny_route(x2d, wt, b):
+                y = _skinny(x2d, wt, b)
+            else:
+                y = _LinearKN.apply(x2d, w, b)
     return y.view(shp)
 
 
@@ -1267,5 +1390,8 @@ def linear_nk(x: torch.Tensor, w: torch.Tensor, b=None) -> torch.Tensor:
     else:
         x2d, w, b = autocast_inputs(x2d, w, b)
         with torch.autocast("cuda", enabled=False):
-            y = _LinearNK.apply(x2d, w, b)
+            if skinny_route(x2d, w, b):  # a decode step: bias included, no autograd node
+                y = _skinny(x2d, w, b)
+            else:
+                y = _LinearNK.apply(x2d, w, b)
     return y.view(shp)

@@ -5,6 +5,8 @@
     python generate.py --model_name_or_path ./sft/final_merged_checkpoint --prompt_file prompts.txt --bf16 \\
         --do_sample --temperature 0.8 --top_p 0.95 --seed 0
     python generate.py --model_name_or_path llama-2-7b --adapter ./sft/final_checkpoint --prompt "..." --bf16
+    python generate.py --model_name_or_path llama-2-7b --load_in_4bit --adapter ./sft/final_checkpoint \\
+        --prompt "..." --bf16
 
 ``--model_name_or_path`` is a named size (random weights, no hub access) or a local HF directory
 (models/registry.py); ``--adapter`` a peft-format LoRA directory as sft_llama2.py writes it.  A directory without a
@@ -40,6 +42,9 @@ def parse_args(argv=None):
     ap.add_argument("--top_p", type=float, default=1.0)
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--bf16", action="store_true")
+    ap.add_argument("--load_in_4bit", action="store_true",
+                    help="keep the base model's linear layers in 4 bits (models/quant.py), as sft_llama2.py does")
+    ap.add_argument("--bnb_4bit_quant_type", default="nf4", choices=("nf4", "fp4"))
     ap.add_argument("--device", default=None, help="cuda / cpu (default: cuda when there is one)")
     ap.add_argument("--config_overrides", default=None, help="e.g. n_layer=2,n_embd=128 for a named size")
     return ap.parse_args(argv)
@@ -56,6 +61,15 @@ def main(argv=None):
     device = torch.device(a.device or ("cuda" if torch.cuda.is_available() else "cpu"))
     config = load_config(a.model_name_or_path, a.config_overrides)
     model = build_model(config, a.model_name_or_path, torch_dtype="bfloat16" if a.bf16 else None)
+    if a.load_in_4bit:
+        # the QLoRA base of sft_llama2.py --load_in_4bit: every nn.Linear but the LM head in the 4-bit store,
+        # quantised on the target device (the GPU kernel when there is one); adapters go on top
+        from distributed_lion_pytorch_amd.models.quant import QuantConfig, quantize_model
+
+        if a.bf16:
+            model = model.to(torch.bfloat16)
+        model = quantize_model(model.to(device), QuantConfig(bnb_4bit_quant_type=a.bnb_4bit_quant_type,
+                                                             bnb_4bit_compute_dtype=torch.bfloat16 if a.bf16 else None))
     if a.adapter:
         model = load_adapter(model, a.adapter)
     if a.bf16:

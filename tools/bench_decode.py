@@ -1,17 +1,21 @@
 #!/usr/bin/env python
 """Decode benchmarks (needs the GPU): the decode-attention kernel against the HBM copy rate and against the
-math SDPA path, and end-to-end ``generate`` against the naive recompute loop, with a per-phase split of a decode
-step.  Writes a text report (default profiles/r12/decode.txt).
+math SDPA path, the skinny-M weight GEMMs (bf16 and 4-bit) against the same copy rate and against the general
+dispatch, and end-to-end ``generate`` against the naive recompute loop, with a per-phase split of a decode
+step.  Writes a text report (default profiles/r13/decode.txt).
 
     python tools/bench_decode.py                      # everything
-    python tools/bench_decode.py --skip_e2e           # the kernel table only
+    python tools/bench_decode.py --skip_e2e           # the kernel tables only
     python tools/bench_decode.py --e2e gpt2           # one end-to-end model
+    python tools/bench_decode.py --skip_kernel --skip_skinny --e2e llama3-4bit --ab   # skinny GEMM on / off, interleaved
 
 Method.  Kernel times are device events around ``iters`` back-to-back calls after a warm-up, the calls rotating
 over enough distinct cache buffers that the working set exceeds the 256 MiB Infinity Cache (a decode step of a
 real model does the same: every layer has its own cache) -- otherwise the small shapes would be timed out of
 cache.  Bytes are the K and V bytes a call has to read (B Hkv len D 2 bytes, twice), computed from the shapes; the
-ceiling is the 6.29 TB/s float4-copy rate of MI355X_MICROARCH.md.  End-to-end figures are wall time around a
+ceiling is the 6.29 TB/s float4-copy rate of MI355X_MICROARCH.md.  The skinny-GEMM table instead sums the kernel
+durations of a profiler trace per call (its small shapes' kernels are shorter than a launch, so back-to-back calls
+would time the host) and sweeps 3 x 256 MiB of distinct weights in every measurement.  End-to-end figures are wall time around a
 device synchronise, profiler off; the phase split comes from a separate, profiled run of 16 decode steps after the prefill.
 """
 from __future__ import annotations
@@ -29,7 +33,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from distributed_lion_pytorch_amd.models import KVCache  # noqa: E402
 from distributed_lion_pytorch_amd.models.registry import build_model, load_config  # noqa: E402
-from distributed_lion_pytorch_amd.ops import fused, hip  # noqa: E402
+from distributed_lion_pytorch_amd.ops import fused, hip, linear, quant  # noqa: E402
 
 HBM_COPY_TBS = 6.29  # MI355X_MICROARCH.md: float4 copy
 CACHE_BYTES = 256 << 20
@@ -48,6 +52,24 @@ def _time(fn, n_variants, iters, warmup=3):
     b.record()
     torch.cuda.synchronize()
     return a.elapsed_time(b) * 1e-3 / iters
+
+
+def _device_time(fn, n_variants, iters, warmup=2):
+    """Seconds of kernel time per call: the summed durations of the device-side events of ``iters`` profiled
+    calls (every kernel a call launches, e.g. GEMM + combine, or expansion + GEMM).  Unlike _time it does not
+    see launch gaps, so it stays a kernel time where back-to-back calls are bound by the host's launch rate."""
+    from torch.autograd import DeviceType
+    from torch.profiler import ProfilerActivity, profile
+
+    for i in range(warmup):
+        fn(i % n_variants)
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        for i in range(iters):
+            fn((warmup + i) % n_variants)
+        torch.cuda.synchronize()
+    total = sum(e.time_range.elapsed_us() for e in prof.events() if e.device_type == DeviceType.CUDA)
+    return total * 1e-6 / iters
 
 
 def kernel_table(dev, iters):
@@ -89,11 +111,68 @@ def kernel_table(dev, iters):
     return lines
 
 
+# ------------------------------------------------------------------------------------------ skinny-M GEMMs
+# [N, K] of a decode step's weight GEMMs: Llama-3-8B (q|k|v, o, gate|up, down, LM head), GPT-2 (c_attn, c_proj, c_fc,
+# mlp c_proj, LM head), Qwen2-0.5B's down_proj (K = 64 x 76)
+SKINNY_SHAPES = [(6144, 4096), (4096, 4096), (28672, 4096), (4096, 14336), (128256, 4096),
+                 (2304, 768), (768, 768), (3072, 768), (768, 3072), (50257, 768), (896, 4864)]
+SKINNY_M = (1, 4, 8, 16)
+W4_BYTES = 0.5 + 4.0 / 64  # per weight element: two indices per byte and an fp32 absmax per 64
+
+
+def skinny_table(dev, iters, shapes=SKINNY_SHAPES, rows=SKINNY_M):
+    """Per shape and M: the skinny kernels' device time (kernel + combine pass where K is split over blocks),
+    weight bytes / time against the copy rate, and the parent dispatch on the same operands (bf16: F.linear,
+    i.e. hipBLASLt; 4-bit: expansion to bf16 + F.linear, what Linear4bit did before).  Times are summed kernel
+    durations from a profiler trace (_device_time), not wall time between events: the small shapes' calls are
+    shorter than a launch.  The calls rotate over 3 x 256 MiB of distinct weights, however many that takes."""
+    head = (f"{'N':>6s} {'K':>5s} {'M':>2s} {'splits':>6s} | {'skinny us':>9s} {'TB/s':>5s} {'of copy':>7s} {'F.linear us':>11s} "
+            f"{'speedup':>7s} | {'w4 us':>7s} {'TB/s':>5s} {'of copy':>7s} {'expand+GEMM us':>14s} {'speedup':>7s}")
+    lines = [head]
+    code = quant.code_tensor("nf4", dev)
+    g = torch.Generator(device=dev).manual_seed(0)
+    for N, K in shapes:
+        wbytes = N * K * 2
+        n = max(2, -(-3 * CACHE_BYTES // wbytes))
+        iters = max(iters, n)  # every measurement sweeps the whole set: nothing it reads is left in the cache
+        ws = [torch.randn(N, K, device=dev, dtype=torch.bfloat16, generator=g) for _ in range(n)]
+        q4 = [quant.quantize_4bit(w, code) for w in ws] if (N * K) % 64 == 0 else None
+        scratch = torch.empty(N, K, device=dev, dtype=torch.bfloat16)
+        for M in rows:
+            x = torch.randn(M, K, device=dev, dtype=torch.bfloat16, generator=g)
+            out = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
+            splits, _ = fused.skinny_splits(M, N, K)
+            t_s = _device_time(lambda i: fused.skinny_gemm(x, ws[i], out=out), n, iters)
+            t_p = _device_time(lambda i: F.linear(x, ws[i]), n, iters)
+            tbs = wbytes / t_s / 1e12
+            row = (f"{N:6d} {K:5d} {M:2d} {splits:6d} | {t_s * 1e6:9.1f} {tbs:5.2f} {tbs / HBM_COPY_TBS:7.1%} {t_p * 1e6:11.1f} "
+                   f"{t_p / t_s:6.2f}x |")
+            if q4 is not None:
+                t_q = _device_time(lambda i: fused.skinny_gemm_w4(x, q4[i][0], q4[i][1], code, N, out=out), n, iters)
+
+                def expand(i):
+                    return F.linear(x, quant.dequantize_4bit(q4[i][0], q4[i][1], code, (N, K), out=scratch))
+
+                t_e = _device_time(expand, n, max(5, iters // 4))
+                tbq = N * K * W4_BYTES / t_q / 1e12
+                row += f" {t_q * 1e6:7.1f} {tbq:5.2f} {tbq / HBM_COPY_TBS:7.1%} {t_e * 1e6:14.1f} {t_e / t_q:6.2f}x"
+            else:
+                row += "  (N K is no multiple of 64: no 4-bit store)"
+            lines.append(row)
+            print(row, flush=True)
+        del ws, q4, scratch
+        torch.cuda.empty_cache()
+    return lines
+
+
 # ------------------------------------------------------------------------------------------ end to end
-E2E = {"gpt2": dict(model="gpt2", B=8, prompt=128, new=256), "llama3": dict(model="llama-3-8b", B=8, prompt=512, new=256)}
+E2E = {"gpt2": dict(model="gpt2", B=8, prompt=128, new=256), "llama3": dict(model="llama-3-8b", B=8, prompt=512, new=256),
+       "llama3-b1": dict(model="llama-3-8b", B=1, prompt=512, new=256),
+       "llama3-4bit": dict(model="llama-3-8b", B=8, prompt=512, new=256, quant="nf4")}
 
 PHASES = [("decode_attention", r"decode_attn_kernel|decode_combine_kernel"), ("kv_append", r"kv_append_kernel"),
-          ("LM head scoring", r"lm_score"), ("norms", r"norm"), ("GEMMs (projections, MLP, LM head)", r"Cijk|gemm|GEMM|hipblaslt|rocblas"),
+          ("LM head scoring", r"lm_score"), ("norms", r"norm"), ("4-bit expansion", r"dequant4"),
+          ("GEMMs (projections, MLP, LM head)", r"Cijk|gemm|GEMM|hipblaslt|rocblas|skinny_"),
           ("activation / elementwise / copies", r"swiglu|gelu|elementwise|vectorized|rope|embed|index|copy|Memcpy|Memset|fill")]
 
 
@@ -170,16 +249,61 @@ def phase_split(model, ids, steps=32):
     return out
 
 
-def end_to_end(name, dev, naive_steps):
+def ab_decode(model, ids, steps=32, rounds=3):
+    """Decode steps with the skinny GEMM routing on and off (off: the parent's dispatch, DLION_SKINNY_GEMM=0),
+    the two interleaved: wall ms per step (best and worst round of each) and kernel ms per step (one profiled
+    run of each)."""
+    from torch.autograd import DeviceType
+    from torch.profiler import ProfilerActivity, profile
+
+    cache, h = prefill(model, ids, (2 * rounds + 3) * steps * 2)
+    wall = {True: [], False: []}
+    kern = {}
+    was = linear._SKINNY
+    try:
+        for on in (True, False):
+            linear._SKINNY = on
+            h = decode_steps(model, cache, h, steps)  # warm
+        for _ in range(rounds):
+            for on in (True, False):
+                linear._SKINNY = on
+                t, h = _wall(lambda: decode_steps(model, cache, h, steps))
+                wall[on].append(t / steps * 1e3)
+        for on in (True, False):
+            linear._SKINNY = on
+            with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+                _, h = _wall(lambda: decode_steps(model, cache, h, steps))
+            kern[on] = sum(e.time_range.elapsed_us() for e in prof.events() if e.device_type == DeviceType.CUDA) * 1e-3 / steps
+    finally:
+        linear._SKINNY = was
+    out = []
+    for on in (False, True):
+        out.append(f"    skinny GEMM {'on ' if on else 'off'}: wall {min(wall[on]):.3f} .. {max(wall[on]):.3f} ms per decode step "
+                   f"({rounds} rounds of {steps} steps), kernels {kern[on]:.3f} ms per step")
+    out.append(f"    on / off: wall {min(wall[True]) / min(wall[False]):.3f}, kernels {kern[True] / kern[False]:.3f}")
+    return out
+
+
+def end_to_end(name, dev, naive_steps, ab=False):
     s = E2E[name]
     cfg = load_config(s["model"])
     torch.manual_seed(0)
     with torch.device(dev):
         model = build_model(cfg, native=True).to(dtype=torch.bfloat16)
+    if s.get("quant"):
+        from distributed_lion_pytorch_amd.models.quant import quantize_model
+
+        quantize_model(model, bnb_4bit_quant_type=s["quant"])
     model.eval()
     ids = torch.randint(0, cfg.vocab_size, (s["B"], s["prompt"]), device=dev)
-    lines = [f"{s['model']}: B = {s['B']}, {s['prompt']} prompt + {s['new']} new tokens, bf16, random weights, greedy"]
+    lines = [f"{s['model']}: B = {s['B']}, {s['prompt']} prompt + {s['new']} new tokens, bf16"
+             f"{', ' + s['quant'] + ' base' if s.get('quant') else ''}, random weights, greedy"]
     model.generate(ids, max_new_tokens=8)  # warm-up: code objects, GEMM algorithm choices
+    if ab:
+        lines += ab_decode(model, ids)
+        del model
+        torch.cuda.empty_cache()
+        return lines
     t, out = _wall(lambda: model.generate(ids, max_new_tokens=s["new"]))
     assert out.shape[1] == s["prompt"] + s["new"]
     t_pre, _ = _wall(lambda: model.generate(ids, max_new_tokens=1))
@@ -201,9 +325,13 @@ def end_to_end(name, dev, naive_steps):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--out", default=os.path.join("profiles", "r12", "decode.txt"))
+    ap.add_argument("--out", default=os.path.join("profiles", "r13", "decode.txt"))
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--skip_kernel", action="store_true")
+    ap.add_argument("--skip_skinny", action="store_true")
+    ap.add_argument("--ab", action="store_true",
+                    help="end to end: decode steps with the skinny GEMM routing on and off, interleaved, instead of "
+                         "the generate / naive-loop / phase report")
     ap.add_argument("--skip_e2e", action="store_true")
     ap.add_argument("--e2e", action="append", choices=sorted(E2E), default=None)
     ap.add_argument("--naive_steps", type=int, default=16)
@@ -217,10 +345,15 @@ def main(argv=None):
         report += ["## decode_attention, bf16, every row at full length; K+V bytes over kernel time against the "
                    f"{HBM_COPY_TBS} TB/s float4 copy", ""] + kernel_table(dev, a.iters) + [""]
         print("\n".join(report), flush=True)
+    if not a.skip_skinny:
+        head = ["## skinny-M GEMM (csrc/skinny_gemm.hip), weight bytes over device time (summed kernel durations of a "
+                f"profiler trace) against the {HBM_COPY_TBS} TB/s float4 copy; 4-bit bytes are {W4_BYTES} per element", ""]
+        print("\n".join(head), flush=True)
+        report += head + skinny_table(dev, a.iters) + [""]
     if not a.skip_e2e:
         report += ["## end to end", ""]
         for name in a.e2e or sorted(E2E):
-            lines = end_to_end(name, dev, a.naive_steps)
+            lines = end_to_end(name, dev, a.naive_steps, a.ab)
             print("\n".join(lines), flush=True)
             report += lines + [""]
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
