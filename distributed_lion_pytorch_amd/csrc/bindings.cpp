@@ -285,6 +285,25 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> lm_score(const Tensor& logits, const 
   return {loss, lse, pred, rank};
 }
 
+// the k best columns of read-only logits: (values, ids, lse), see kernels.h
+std::tuple<Tensor, Tensor, Tensor> lm_topk(const Tensor& logits, int64_t v, int64_t k) {
+  check_dev(logits, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous(), "dlion: logits must be a contiguous [N, Vpad]");
+  TORCH_CHECK(logits.size(1) % 8 == 0 && v > 0 && v <= logits.size(1), "dlion: padded vocab must be a multiple of 8");
+  TORCH_CHECK(logits.size(1) <= (int64_t{1} << 30), "dlion: lm_topk vocabulary too wide");
+  TORCH_CHECK(k >= 1 && k <= 64 && k <= v, "dlion: lm_topk needs 1 <= k <= 64 and k <= v, got k = ", k, ", v = ", v);
+  const c10::DeviceGuard g(logits.device());
+  const int64_t n = logits.size(0);
+  auto values = at::empty({n, k}, logits.options().dtype(at::kFloat));
+  auto ids = at::empty({n, k}, logits.options().dtype(at::kInt));
+  auto lse = at::empty({n}, logits.options().dtype(at::kFloat));
+  check_hip(dlion::launch_lm_topk(dtype_code(logits.scalar_type()), logits.data_ptr(), n, logits.size(1),
+                                  static_cast<int>(v), static_cast<int>(k), values.data_ptr<float>(),
+                                  ids.data_ptr<int>(), lse.data_ptr<float>(), cur_stream()),
+            "lm_topk");
+  return {values, ids, lse};
+}
+
 // ------------------------------------------------------------ flash attention
 void check_bthd(const Tensor& t, const char* name) {
   TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16, "dlion attn: ", name, " must be a bf16 GPU tensor");
@@ -1593,6 +1612,7 @@ TORCH_LIBRARY(dlion, m) {
   m.def("softmax_xent_(Tensor(a!) logits, Tensor labels, int v, int variant=0) -> Tensor");
   m.def("softmax_xent_opts_(Tensor(a!) logits, Tensor labels, int v, float smoothing, float z_loss, int variant=0) -> Tensor");
   m.def("lm_score(Tensor logits, Tensor labels, int v, float smoothing, float z_loss) -> (Tensor, Tensor, Tensor, Tensor)");
+  m.def("lm_topk(Tensor logits, int v, int k) -> (Tensor, Tensor, Tensor)");
   m.def(
       "lion_local(Tensor meta, int seg_off, int chunk_off, int n_chunks, int dtype, float decay, float neg_lr,"
       " float b1, float omb1, float b2, float omb2, Tensor? gscale=None, int rounding=0, int rkey=0,"
@@ -1624,6 +1644,7 @@ TORCH_LIBRARY_IMPL(dlion, CUDA, m) {
   m.impl("softmax_xent_", &softmax_xent_);
   m.impl("softmax_xent_opts_", &softmax_xent_opts_);
   m.impl("lm_score", &lm_score);
+  m.impl("lm_topk", &lm_topk);
   m.impl("attn_fwd", &attn_fwd);
   m.impl("attn_bwd", &attn_bwd);
   m.impl("add_norm_fwd", &add_norm_fwd);

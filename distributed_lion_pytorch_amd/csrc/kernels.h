@@ -176,6 +176,12 @@ hipError_t launch_softmax_xent_opts(int dt, void* logits, const int64_t* labels,
 hipError_t launch_lm_score(int dt, const void* logits, const int64_t* labels, int64_t n, int64_t vp, int v, float eps,
                            float zeta, float* row_loss, float* row_lse, int* pred, int* rank, hipStream_t st);
 
+// ---- LM head top-k, forward only (lm_topk.hip): read-only logits [n, vp], real columns j < v, 1 <= k <= 64, k <= v
+// ids [n, k] = the first k columns under (greater value, then lower column; values compared as floats),
+// values [n, k] = the stored logits there, lse [n] = logsumexp; one launch, no float atomics
+hipError_t launch_lm_topk(int dt, const void* logits, int64_t n, int64_t vp, int v, int k, float* values, int* ids,
+                          float* lse, hipStream_t st);
+
 // ---- generation (decode.hip); bf16, D in {64, 128}
 // One decode step's q [B, H, D] / k / v [B, Hkv, D] (row strides *_ld, heads contiguous): q and k normed (gains
 // nullable, Qwen3) and rotated (tables [>= Tmax, D], nullable) at pos[b], clamped into [0, Tmax) with

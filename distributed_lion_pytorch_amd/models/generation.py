@@ -7,13 +7,14 @@ prompt through the flash forward), every later call one decode step (one token p
 ``fused.kv_append`` and ``fused.decode_attention``, csrc/decode.hip).
 
 ``NativeGenerateMixin.generate`` uses HF's argument names: greedy or sampled (temperature, then top-k, then
-top-p), ragged prompts by ``attention_mask`` (left- or right-padded), EOS / pad handling.  Out of scope: beam
-search, repetition penalties, a paged or rolling cache (a windowed layer keeps its full-length cache and only
+top-p), ragged prompts by ``attention_mask`` (left- or right-padded), EOS / pad handling; ``num_beams > 1`` is beam
+search (HF's semantics) on ``fused.lm_head_topk``.  Out of scope: beam sampling, diverse / constrained beams,
+repetition penalties, a paged or rolling cache (a windowed layer keeps its full-length cache and only
 bounds the key range), graph capture, speculative decoding.
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -21,6 +22,14 @@ from ..ops import fused
 from ..ops.linear import gemm_fwd
 
 _EOS_CHECK_EVERY = 8  # decode steps between two host reads of "every row has finished"
+
+
+class GenerateOutput(NamedTuple):
+    """``generate(..., return_dict_in_generate=True)``: ``sequences`` [rows, T0 + n_new] and, for beam search,
+    ``sequences_scores`` [rows]: the sum of the new tokens' log-probabilities / (their number ** length_penalty)."""
+
+    sequences: torch.Tensor
+    sequences_scores: Optional[torch.Tensor]
 
 
 def cache_geometry(config):
@@ -81,6 +90,34 @@ class KVCache:
         """Ragged prompts, left-aligned in the prefill: row b holds ``lengths[b]`` <= width real tokens."""
         self.lengths.copy_(lengths.to(self.lengths.dtype))
 
+    def repeat_rows(self, n: int) -> "KVCache":
+        """A new cache of batch ``batch * n`` whose rows b n .. b n + n - 1 hold row b (beam search after one
+        prefill per prompt): only the positions below ``width`` are copied, the lengths are repeated."""
+        n = int(n)
+        if n < 1:
+            raise ValueError("KVCache.repeat_rows: n must be >= 1")
+        out = object.__new__(KVCache)
+        out.batch, out.max_len = self.batch * n, self.max_len
+        shape = list(self._buf.shape)
+        shape[2] = out.batch
+        out._buf = torch.zeros(shape, device=self._buf.device, dtype=self._buf.dtype)
+        w = self.width
+        out._buf[:, :, :, :w] = self._buf[:, :, :, :w].repeat_interleave(n, dim=2)
+        out.lengths = self.lengths.repeat_interleave(n)
+        out.kv_len = out.lengths
+        out.width, out.prefilled = self.width, self.prefilled
+        return out
+
+    def reorder_rows(self, index: torch.Tensor, lo: int = 0) -> None:
+        """Row r takes the contents of row ``index[r]`` (beam search: the beam it continues) at the positions
+        ``lo <= t < width``, and its length.  Below ``lo`` the caller vouches that the rows exchanged hold the
+        same keys (a shared prompt), so the move costs the generated suffix, not the context."""
+        lo = max(0, int(lo))
+        if lo < self.width:
+            part = self._buf[:, :, :, lo:self.width]
+            self._buf[:, :, :, lo:self.width] = part.index_select(2, index)
+        self.lengths.copy_(self.lengths.index_select(0, index))
+
 
 # ------------------------------------------------------------------------------------------ prompts
 def left_align(input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor]):
@@ -135,14 +172,32 @@ class NativeGenerateMixin:
     def generate(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
                  max_new_tokens: int = 20, do_sample: bool = False, temperature: float = 1.0, top_k: int = 0,
                  top_p: float = 1.0, eos_token_id=None, pad_token_id: Optional[int] = None,
-                 seed: Optional[int] = None) -> torch.Tensor:
+                 seed: Optional[int] = None, num_beams: int = 1, num_return_sequences: int = 1,
+                 length_penalty: float = 1.0, early_stopping: bool = False, return_dict_in_generate: bool = False):
         """[B, T0] prompts -> [B, T0 + n_new] long: the prompt exactly as given, then the new tokens.
 
         Greedy takes the top-1 of ``fused.lm_head_score`` (the lowest id on ties, no [B, V] tensor); sampling
         warps the last hidden states' logits (temperature, top-k, top-p) and draws with ``torch.multinomial``
         from a generator seeded by ``seed``.  Rows that emitted ``eos_token_id`` (int or list) produce
         ``pad_token_id`` (default: the first EOS id) from then on; generation ends once every row has finished
-        (read from the device every 8 steps; the result is trimmed to the step at which the last row finished)."""
+        (read from the device every 8 steps; the result is trimmed to the step at which the last row finished).
+
+        ``num_beams > 1`` is beam search with the semantics of transformers' ``generate(num_beams=n,
+        do_sample=False)``: ``num_return_sequences`` rows per prompt, best first ([B * num_return_sequences,
+        T0 + n_new]), ``length_penalty`` and ``early_stopping`` (False or True) as there; every step takes the
+        ``max(2, 1 + #eos) * num_beams`` best continuations of every live beam from ``fused.lm_head_topk``.
+        ``return_dict_in_generate=True`` returns :class:`GenerateOutput` (``sequences``, ``sequences_scores``; the
+        scores are None without beams)."""
+        num_beams, num_return_sequences = int(num_beams), int(num_return_sequences)
+        if num_beams < 1:
+            raise ValueError("generate: num_beams must be >= 1")
+        if num_return_sequences < 1 or num_return_sequences > num_beams:
+            raise ValueError("generate: num_return_sequences must be in [1, num_beams]"
+                             + (" (more than one sequence per prompt needs num_beams > 1)" if num_beams == 1 else ""))
+        if num_beams > 1 and do_sample:
+            raise ValueError("generate: num_beams > 1 with do_sample=True (beam sampling) is not supported")
+        if not isinstance(early_stopping, bool):
+            raise ValueError(f"generate: early_stopping must be False or True, got {early_stopping!r}")
         if self.training:
             raise ValueError("generate: the model is in training mode; call model.eval() first")
         if input_ids.dim() != 2 or input_ids.shape[1] < 1:
@@ -168,6 +223,12 @@ class NativeGenerateMixin:
                 pad_token_id = int(eos[0])
         ids, lens = left_align(input_ids, attention_mask)
         weight = self.lm_head.weight
+        if num_beams > 1:
+            lo = T0 if attention_mask is None else int(lens.min())
+            out = self._beam_search(input_ids, ids, lens, lo, max_new_tokens, eos, pad_token_id, num_beams,
+                                    num_return_sequences, float(length_penalty), early_stopping)
+            fused.check_index_errors()
+            return out if return_dict_in_generate else out.sequences
         cache = KVCache(cfg, B, total, dev, weight.dtype)
         gen = None
         if do_sample and seed is not None:
@@ -205,4 +266,86 @@ class NativeGenerateMixin:
             if last < max_new_tokens:
                 n_new = last + 1
         fused.check_index_errors()
-        return torch.cat([input_ids, new[:, :n_new]], dim=1)
+        out = torch.cat([input_ids, new[:, :n_new]], dim=1)
+        return GenerateOutput(out, None) if return_dict_in_generate else out
+
+    def _beam_search(self, input_ids, ids, lens, lo, n, eos, pad_token_id, nb, n_ret, length_penalty, early_stopping):
+        """transformers' ``GenerationMixin._beam_search`` on the native cache: the same running / finished beam
+        sets, scores and stopping rules, with two differences in mechanics.  The candidates of a step are the
+        ``keep`` best continuations of every beam (``fused.lm_head_topk``: values - logsumexp are the
+        log-probabilities) instead of a [B, num_beams * V] log-softmax -- a beam's continuation outside its own
+        best ``keep`` cannot be among the batch row's best ``keep``.  And the prompt is prefilled once per row,
+        its cache rows repeated (``KVCache.repeat_rows``), and every step moves only the generated suffix
+        between the beams of a row (``KVCache.reorder_rows``).  One host read per step (HF reads the same flag)."""
+        B, T0 = input_ids.shape
+        dev = input_ids.device
+        cfg, weight, base = self.config, self.lm_head.weight, self._decoder()
+        keep = max(2, 1 + (0 if eos is None else int(eos.numel()))) * nb
+        if keep > fused.LM_TOPK_MAX or keep > cfg.vocab_size:
+            raise ValueError(f"generate: num_beams = {nb} keeps {keep} candidates per beam; at most "
+                             f"{min(fused.LM_TOPK_MAX, cfg.vocab_size)} (the top-k kernel's k, the vocabulary) fit")
+        fill = pad_token_id if pad_token_id is not None else 0
+        rows = torch.arange(B, device=dev)
+        first = KVCache(cfg, B, T0 + n, dev, weight.dtype)
+        h = base(ids, cache=first)[rows, lens - 1]  # one prefill per prompt
+        first.set_lengths(lens)
+        cache = first.repeat_rows(nb)
+        del first
+        h = h.repeat_interleave(nb, dim=0)
+
+        run_seq = torch.full((B, nb, n), fill, dtype=torch.long, device=dev)
+        fin_seq = run_seq.clone()
+        run_scores = torch.zeros(B, nb, dtype=torch.float32, device=dev)
+        run_scores[:, 1:] = -1e9  # the beams of a row start equal: only the first may be continued
+        fin_scores = torch.full((B, nb), -1e9, dtype=torch.float32, device=dev)
+        fin_done = torch.zeros(B, nb, dtype=torch.bool, device=dev)
+        fin_len = torch.zeros(B, nb, dtype=torch.long, device=dev)
+        unsat = torch.ones(B, 1, dtype=torch.bool, device=dev)  # the open beams may still beat the finished ones
+        top_mask = torch.arange(keep, device=dev) < nb
+        offset = (rows * nb)[:, None]
+        for i in range(n):
+            top = fused.lm_head_topk(h, weight, keep)
+            logp = (top.values - top.lse[:, None]) + run_scores.view(-1, 1)
+            cand_lp, pick = torch.topk(logp.view(B, nb * keep), keep)
+            cand_beam = pick // keep
+            tok = top.ids.view(B, nb * keep).gather(1, pick).long()
+            cand_seq = run_seq.gather(1, cand_beam[:, :, None].expand(-1, -1, n))
+            cand_seq[:, :, i] = tok
+            if i + 1 == n:
+                hits = torch.ones_like(tok, dtype=torch.bool)
+            elif eos is not None:
+                hits = torch.isin(tok, eos)
+            else:
+                hits = torch.zeros_like(tok, dtype=torch.bool)
+            # the open beams of the next step: the best candidates that did not stop
+            run_lp = cand_lp + hits.to(torch.float32) * -1.0e9
+            nxt = torch.topk(run_lp, nb)[1]
+            run_seq = cand_seq.gather(1, nxt[:, :, None].expand(-1, -1, n))
+            run_scores = run_lp.gather(1, nxt)
+            beam_idx = (cand_beam.gather(1, nxt) + offset).reshape(-1)
+            # the finished set: candidates among the best num_beams that stopped, merged with the earlier ones
+            did = hits & top_mask[None, :]
+            fin_lp = cand_lp / ((i + 1) ** length_penalty)
+            full = fin_done.all(dim=-1, keepdim=True) & (early_stopping is True)
+            fin_lp = fin_lp + full.to(torch.float32) * -1.0e9
+            fin_lp = fin_lp + (~unsat).to(torch.float32) * -1.0e9
+            fin_lp = fin_lp + (~did) * -1.0e9
+            m_scores = torch.cat((fin_scores, fin_lp), dim=1)
+            best = torch.topk(m_scores, nb)[1]
+            fin_seq = torch.cat((fin_seq, cand_seq), dim=1).gather(1, best[:, :, None].expand(-1, -1, n))
+            fin_scores = m_scores.gather(1, best)
+            fin_done = torch.cat((fin_done, did), dim=1).gather(1, best)
+            fin_len = torch.cat((fin_len, torch.full_like(tok, i + 1)), dim=1).gather(1, best)
+            # can an open beam still beat the worst finished one (HF's heuristic for early_stopping=False)?
+            best_open = run_scores[:, :1] / ((i + 1) ** length_penalty)
+            worst = torch.where(fin_done, fin_scores.min(dim=1, keepdim=True)[0], -1.0e9)
+            unsat = unsat & torch.any(best_open > worst, dim=-1, keepdim=True)
+            go_on = torch.any(unsat) & ~(torch.all(fin_done) & (early_stopping is True)) & ~torch.all(hits)
+            if not bool(go_on):  # the one host read of the step
+                break
+            cache.reorder_rows(beam_idx, lo)
+            h = base(run_seq[:, :, i].reshape(-1, 1), cache=cache)[:, 0]
+        seqs = fin_seq[:, :n_ret].reshape(B * n_ret, n)
+        n_new = int(fin_len[:, :n_ret].max())
+        out = torch.cat([input_ids.repeat_interleave(n_ret, dim=0), seqs[:, :n_new]], dim=1)
+        return GenerateOutput(out, fin_scores[:, :n_ret].reshape(-1))

@@ -2022,6 +2022,63 @@ def causal_lm_score(h: torch.Tensor, weight: torch.Tensor, labels: torch.Tensor,
                          normalizer=normalizer)
 
 
+# --------------------------------------------- LM head top-k (forward only)
+class LMTopK(NamedTuple):
+    """What :func:`lm_head_topk` returns per row of the head's logits: the ``k`` best
+    stored logits ``values`` [N, k] (fp32), their token ``ids`` [N, k] (int32) and the
+    logsumexp ``lse`` [N] (fp32); ``values - lse[:, None]`` are the log-probabilities."""
+
+    values: torch.Tensor
+    ids: torch.Tensor
+    lse: torch.Tensor
+
+
+LM_TOPK_MAX = 64  # the kernel's k (csrc/lm_topk.hip); a larger k takes the PyTorch form
+
+
+def _lm_topk_torch(logits: torch.Tensor, v: int, k: int):
+    """PyTorch form of the top-k kernel (csrc/lm_topk.hip) on logits [N, Vp], real
+    columns j < v: the first k columns of a stable descending sort of the fp32 values
+    (greater value first, the lower column among equal values, -0.0 == +0.0), the
+    stored values there and the fp32 logsumexp."""
+    if not 1 <= k <= v:
+        raise ValueError(f"dlion: lm_topk needs 1 <= k <= v, got k = {k}, v = {v}")
+    x = logits[:, :v].float()
+    srt, order = torch.sort(x, dim=1, descending=True, stable=True)
+    return srt[:, :k].contiguous(), order[:, :k].to(torch.int32), torch.logsumexp(x, dim=1)
+
+
+def lm_head_topk(h: torch.Tensor, weight: torch.Tensor, k: int) -> LMTopK:
+    """The ``k`` best tokens of the LM head ``h @ weight.T`` per row without keeping
+    logits: one GEMM into a transient [N, Vp] block and one read-only kernel pass
+    over it (csrc/lm_topk.hip, ``k <= 64``).  Order: greater logit first, the lower
+    id among equal logits (a stable descending sort; not ``torch.topk``, whose tie
+    order is unspecified).  Forward only, as :func:`lm_head_score`."""
+    if torch.is_grad_enabled() and (h.requires_grad or weight.requires_grad):
+        raise RuntimeError("dlion: lm_head_topk is forward-only (no gradient reaches h or the weight); "
+                           "call it under torch.no_grad()")
+    k = int(k)
+    with torch.no_grad():
+        h2d = h.reshape(-1, h.shape[-1])
+        v = weight.shape[0]
+        if not 1 <= k <= v:
+            raise ValueError(f"dlion: lm_head_topk needs 1 <= k <= vocabulary ({v}), got {k}")
+        if h2d.is_cuda:
+            from .linear import autocast_inputs
+
+            h2d, weight = autocast_inputs(h2d, weight)
+        elif h2d.dtype != weight.dtype:
+            h2d = h2d.to(weight.dtype)
+        with torch.autocast("cuda", enabled=False) if h2d.is_cuda else contextlib.nullcontext():
+            logits = gemm_fwd(h2d, _pad_rows(weight))  # [N, Vp] in the compute dtype, read-only below
+            if logits.dtype in _SCORE_DTYPES and k <= LM_TOPK_MAX and _use_hip(logits):
+                values, ids, lse = hip.ops().lm_topk(logits.contiguous(), v, k)
+            else:
+                values, ids, lse = _lm_topk_torch(logits, v, k)
+            del logits
+        return LMTopK(values, ids, lse)
+
+
 def token_predictions(logits, labels=None):
     """``preprocess_logits_for_metrics`` of the package: the (predictions,
     label_ranks) pair of a scored evaluation step passes through; full logits

@@ -5,6 +5,7 @@
     python generate.py --model_name_or_path ./sft/final_merged_checkpoint --prompt_file prompts.txt --bf16 \\
         --do_sample --temperature 0.8 --top_p 0.95 --seed 0
     python generate.py --model_name_or_path llama-2-7b --adapter ./sft/final_checkpoint --prompt "..." --bf16
+    python generate.py --model_name_or_path gpt2 --prompt "The quick brown fox" --num_beams 4 --num_return_sequences 2
     python generate.py --model_name_or_path llama-2-7b --load_in_4bit --adapter ./sft/final_checkpoint \\
         --prompt "..." --bf16
 
@@ -41,6 +42,10 @@ def parse_args(argv=None):
     ap.add_argument("--top_k", type=int, default=0)
     ap.add_argument("--top_p", type=float, default=1.0)
     ap.add_argument("--seed", type=int, default=None)
+    ap.add_argument("--num_beams", type=int, default=1, help="beam search (greedy only; HF's semantics)")
+    ap.add_argument("--num_return_sequences", type=int, default=1, help="beams returned per prompt, best first")
+    ap.add_argument("--length_penalty", type=float, default=1.0)
+    ap.add_argument("--early_stopping", action="store_true")
     ap.add_argument("--bf16", action="store_true")
     ap.add_argument("--load_in_4bit", action="store_true",
                     help="keep the base model's linear layers in 4 bits (models/quant.py), as sft_llama2.py does")
@@ -101,16 +106,20 @@ def main(argv=None):
     t0 = time.perf_counter()
     out = model.generate(ids, attention_mask=mask, max_new_tokens=a.max_new_tokens, do_sample=a.do_sample,
                          temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, eos_token_id=eos,
-                         pad_token_id=pad if eos is not None else None, seed=a.seed)
+                         pad_token_id=pad if eos is not None else None, seed=a.seed, num_beams=a.num_beams,
+                         num_return_sequences=a.num_return_sequences, length_penalty=a.length_penalty,
+                         early_stopping=a.early_stopping)
     sync()
     dt = time.perf_counter() - t0
     new = out[:, width:].tolist()
     n_tokens = 0
-    for p, r in zip(prompts, new):
+    per = a.num_return_sequences  # rows per prompt, best beam first
+    for j, r in enumerate(new):
+        p = prompts[j // per]
         if eos is not None and eos in r:
             r = r[:r.index(eos)]
         n_tokens += len(r)
-        print(f"--- {p!r}\n{tok.decode(r)}")
+        print(f"--- {p!r}{f' [beam {j % per}]' if per > 1 else ''}\n{tok.decode(r)}")
     print(f"[generate] {len(prompts)} prompt(s), {out.shape[1] - width} steps, {n_tokens} new tokens in {dt:.3f} s: "
           f"{n_tokens / dt:.1f} tokens/s on {device}")
     return out

@@ -2,12 +2,15 @@
 """Decode benchmarks (needs the GPU): the decode-attention kernel against the HBM copy rate and against the
 math SDPA path, the skinny-M weight GEMMs (bf16 and 4-bit) against the same copy rate and against the general
 dispatch, and end-to-end ``generate`` against the naive recompute loop, with a per-phase split of a decode
-step.  Writes a text report (default profiles/r13/decode.txt).
+step; the LM-head top-k kernel against the PyTorch chain and beam search end to end (``--topk``,
+``--num_beams``).  Writes a text report (default profiles/r13/decode.txt).
 
     python tools/bench_decode.py                      # everything
     python tools/bench_decode.py --skip_e2e           # the kernel tables only
     python tools/bench_decode.py --e2e gpt2           # one end-to-end model
     python tools/bench_decode.py --skip_kernel --skip_skinny --e2e llama3-4bit --ab   # skinny GEMM on / off, interleaved
+    python tools/bench_decode.py --skip_kernel --skip_skinny --topk --num_beams 4 --e2e gpt2 --e2e llama3 \
+        --out profiles/r14/beam.txt                   # the top-k kernel table and beam search next to greedy
 
 Method.  Kernel times are device events around ``iters`` back-to-back calls after a warm-up, the calls rotating
 over enough distinct cache buffers that the working set exceeds the 256 MiB Infinity Cache (a decode step of a
@@ -165,6 +168,45 @@ def skinny_table(dev, iters, shapes=SKINNY_SHAPES, rows=SKINNY_M):
     return lines
 
 
+# ------------------------------------------------------------------------------------------ LM-head top-k
+TOPK_CASES = [(N, V, k) for V in (50257, 128256) for N in (8, 16, 64) for k in (8, 64)]
+
+
+def topk_table(dev, iters):
+    """csrc/lm_topk.hip against the PyTorch chain a beam step would otherwise run on the same bf16 logits
+    (log_softmax in fp32, then topk): summed kernel durations of a profiler trace per call (_device_time; the
+    calls are shorter than a launch gap) and the bytes the chain allocates at its peak (the kernel allocates its
+    three outputs, (8 k + 4) N bytes).  The logits rotate over 4 buffers that together stay inside the L2 /
+    Infinity Cache: in a decode step the head GEMM has just written them."""
+    lines = [f"{'N':>3s} {'V':>6s} {'k':>2s} {'kernel us':>9s} {'row read TB/s':>13s} {'chain us':>8s} {'log_softmax us':>14s} "
+             f"{'topk us':>7s} {'chain / kernel':>14s} {'chain allocates':>15s}"]
+    g = torch.Generator(device=dev).manual_seed(0)
+    for N, V, k in TOPK_CASES:
+        vp = (V + 63) // 64 * 64
+        xs = [(2 * torch.randn(N, vp, device=dev, generator=g)).bfloat16() for _ in range(4)]
+        t_k = _device_time(lambda i: hip.ops().lm_topk(xs[i], V, k), 4, iters)
+        t_l = _device_time(lambda i: torch.log_softmax(xs[i][:, :V].float(), -1), 4, iters)
+        lp = torch.log_softmax(xs[0][:, :V].float(), -1)
+        t_t = _device_time(lambda i: torch.topk(lp, k, dim=-1), 4, iters)
+        del lp
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        out = torch.topk(torch.log_softmax(xs[0][:, :V].float(), -1), k, dim=-1)
+        torch.cuda.synchronize()
+        peak = torch.cuda.max_memory_allocated() - base
+        # same selection on rows without ties at the k-th place (topk's tie order is unspecified)
+        values, ids, lse = hip.ops().lm_topk(xs[0], V, k)
+        same = float((values - lse[:, None] - out.values).abs().max())
+        row = (f"{N:3d} {V:6d} {k:2d} {t_k * 1e6:9.1f} {N * V * 2 / t_k / 1e12:13.2f} {(t_l + t_t) * 1e6:8.1f} {t_l * 1e6:14.1f} "
+               f"{t_t * 1e6:7.1f} {(t_l + t_t) / t_k:13.2f}x {peak / 2 ** 20:11.1f} MiB   max |log-prob diff| {same:.1e}")
+        lines.append(row)
+        print(row, flush=True)
+        del xs, out
+        torch.cuda.empty_cache()
+    return lines
+
+
 # ------------------------------------------------------------------------------------------ end to end
 E2E = {"gpt2": dict(model="gpt2", B=8, prompt=128, new=256), "llama3": dict(model="llama-3-8b", B=8, prompt=512, new=256),
        "llama3-b1": dict(model="llama-3-8b", B=1, prompt=512, new=256),
@@ -284,6 +326,55 @@ def ab_decode(model, ids, steps=32, rounds=3):
     return out
 
 
+def reorder_times(model, rows, num_beams, prompt, new, iters=50):
+    """Seconds per KVCache.reorder_rows of a [rows]-row cache at generated suffixes of 1, new / 2 and new - 1
+    positions above the prompt (device events around back-to-back calls)."""
+    dev = model.lm_head.weight.device
+    cache = KVCache(model.config, rows, prompt + new, dev, model.lm_head.weight.dtype)
+    cache.prefilled = True
+    index = (torch.arange(rows, device=dev) // num_beams) * num_beams + torch.randint(0, num_beams, (rows,), device=dev)
+    out = []
+    for suffix in (1, new // 2, new - 1):
+        cache.width = prompt + suffix
+        out.append((suffix, _time(lambda i: cache.reorder_rows(index, prompt), 1, iters)))
+    return out
+
+
+def beam_end_to_end(name, dev, num_beams):
+    """Beam search at B / num_beams prompts against greedy at B rows on the same model: the decode kernels and
+    the GEMMs see the same M."""
+    s = E2E[name]
+    cfg = load_config(s["model"])
+    torch.manual_seed(0)
+    with torch.device(dev):
+        model = build_model(cfg, native=True).to(dtype=torch.bfloat16)
+    model.eval()
+    rows, Bb, new = s["B"], s["B"] // num_beams, s["new"]
+    ids = torch.randint(0, cfg.vocab_size, (rows, s["prompt"]), device=dev)
+    kw = dict(num_beams=num_beams, num_return_sequences=num_beams)
+    lines = [f"{s['model']}: {s['prompt']} prompt + {new} new tokens, bf16, random weights; beam search B = {Bb} x "
+             f"{num_beams} beams against greedy B = {rows} ({rows} rows per decode step either way)"]
+    model.generate(ids, max_new_tokens=8)
+    model.generate(ids[:Bb], max_new_tokens=8, **kw)  # warm-up: code objects, GEMM algorithm choices
+    per = {}
+    for rnd in range(2):  # the two alternate; the better round of each is reported, both are printed
+        for what, call in (("greedy", lambda n: model.generate(ids, max_new_tokens=n)),
+                           ("beam", lambda n: model.generate(ids[:Bb], max_new_tokens=n, **kw))):
+            t, out = _wall(lambda: call(new))
+            assert out.shape == (rows, s["prompt"] + new), out.shape
+            t1, _ = _wall(lambda: call(1))
+            per.setdefault(what, []).append((t - t1) / (new - 1) * 1e3)
+            lines.append(f"  round {rnd} {what:6s}: {t:.3f} s, prefill + first token {t1 * 1e3:.1f} ms, "
+                         f"{per[what][-1]:.3f} ms per step")
+    g, b = min(per["greedy"]), min(per["beam"])
+    lines.append(f"  ms per step: beam {b:.3f}, greedy {g:.3f}, beam / greedy {b / g:.3f}")
+    for suffix, t in reorder_times(model, rows, num_beams, s["prompt"], new):
+        lines.append(f"  reorder_rows at a suffix of {suffix:3d} positions: {t * 1e6:8.1f} us, {t * 1e3 / b:6.1%} of a beam step")
+    del model
+    torch.cuda.empty_cache()
+    return lines
+
+
 def end_to_end(name, dev, naive_steps, ab=False):
     s = E2E[name]
     cfg = load_config(s["model"])
@@ -335,6 +426,10 @@ def main(argv=None):
     ap.add_argument("--skip_e2e", action="store_true")
     ap.add_argument("--e2e", action="append", choices=sorted(E2E), default=None)
     ap.add_argument("--naive_steps", type=int, default=16)
+    ap.add_argument("--topk", action="store_true", help="the LM-head top-k kernel table (csrc/lm_topk.hip)")
+    ap.add_argument("--num_beams", type=int, default=1,
+                    help="end to end: beam search at B / num_beams prompts next to greedy at B rows, instead of the "
+                         "generate / naive-loop / phase report")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("bench_decode.py measures on the GPU; there is none here")
@@ -350,10 +445,18 @@ def main(argv=None):
                 f"profiler trace) against the {HBM_COPY_TBS} TB/s float4 copy; 4-bit bytes are {W4_BYTES} per element", ""]
         print("\n".join(head), flush=True)
         report += head + skinny_table(dev, a.iters) + [""]
+    if a.topk:
+        head = ["## LM-head top-k (csrc/lm_topk.hip) against log_softmax (fp32) + topk on the same bf16 logits; device "
+                "time = summed kernel durations of a profiler trace", ""]
+        print("\n".join(head), flush=True)
+        report += head + topk_table(dev, a.iters) + [""]
     if not a.skip_e2e:
         report += ["## end to end", ""]
         for name in a.e2e or sorted(E2E):
-            lines = end_to_end(name, dev, a.naive_steps, a.ab)
+            if a.num_beams > 1:
+                lines = beam_end_to_end(name, dev, a.num_beams)
+            else:
+                lines = end_to_end(name, dev, a.naive_steps, a.ab)
             print("\n".join(lines), flush=True)
             report += lines + [""]
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
