@@ -1472,6 +1472,121 @@ Tensor decode_attention(const Tensor& q, const Tensor& k_cache, const Tensor& v_
             "decode_attention");
   return out;
 }
+
+// ---- generation, T tokens per sequence (csrc/chunk_attention.hip)
+// x [B, T, heads, D] bf16 with contiguous heads and 16-byte aligned token / batch strides (a column view of the
+// fused q|k|v projection output)
+void check_chunk_rows(const char* what, const char* name, const Tensor& x, int64_t B, int64_t T, int64_t D) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 4 && x.scalar_type() == at::kBFloat16 && x.size(0) == B && x.size(1) == T &&
+                  x.size(3) == D && x.size(2) >= 1 && x.stride(3) == 1 && (x.size(2) == 1 || x.stride(2) == D) &&
+                  (T == 1 || (x.stride(1) % 8 == 0 && x.stride(1) >= x.size(2) * D)) &&
+                  (B == 1 || (x.stride(0) % 8 == 0 && x.stride(0) >= T * (T == 1 ? x.size(2) * D : x.stride(1)))) &&
+                  reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "dlion ", what, ": ", name,
+              " must be bf16 [B, T, heads, D] with contiguous heads and 16-byte aligned token / batch strides");
+}
+int64_t chunk_token_stride(const Tensor& x) { return x.size(1) == 1 ? x.size(2) * x.size(3) : x.stride(1); }
+int64_t chunk_batch_stride(const Tensor& x) { return x.size(0) == 1 ? x.size(1) * chunk_token_stride(x) : x.stride(0); }
+const int* chunk_n_new(const char* what, const std::optional<Tensor>& n_new, int64_t B) {
+  if (!n_new.has_value()) return nullptr;
+  TORCH_CHECK(n_new->is_cuda() && n_new->scalar_type() == at::kInt && n_new->is_contiguous() && n_new->numel() == B,
+              "dlion ", what, ": n_new must be a contiguous int32 [B] GPU tensor");
+  return n_new->data_ptr<int>();
+}
+
+// returns the normed / rotated q [B, T, H, D]; k (normed / rotated) and v of the tokens t < n_new[b] go to
+// cache[b, pos[b] + t]
+Tensor kv_append_chunk(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& pos,
+                       const std::optional<Tensor>& n_new, const std::optional<Tensor>& cos,
+                       const std::optional<Tensor>& sin, const std::optional<Tensor>& q_gamma,
+                       const std::optional<Tensor>& k_gamma, double eps, const Tensor& k_cache, const Tensor& v_cache,
+                       const Tensor& err) {
+  TORCH_CHECK(q.dim() == 4, "dlion kv_append_chunk: q must be [B, T, H, D]");
+  const int64_t B = q.size(0), T = q.size(1), H = q.size(2), D = q.size(3);
+  TORCH_CHECK(D == 64 || D == 128, "dlion kv_append_chunk: head_dim must be 64 or 128");
+  TORCH_CHECK(T >= 1 && T <= dlion::kChunkMaxTokens, "dlion kv_append_chunk: T must be in [1, 8]");
+  TORCH_CHECK(k.dim() == 4 && v.dim() == 4 && k.size(2) == v.size(2), "dlion kv_append_chunk: k / v must be [B, T, Hkv, D]");
+  const int64_t Hkv = k.size(2);
+  check_chunk_rows("kv_append_chunk", "q", q, B, T, D);
+  check_chunk_rows("kv_append_chunk", "k", k, B, T, D);
+  check_chunk_rows("kv_append_chunk", "v", v, B, T, D);
+  check_cache("kv_append_chunk", "k_cache", k_cache, B, Hkv, D);
+  check_cache("kv_append_chunk", "v_cache", v_cache, B, Hkv, D);
+  const int64_t Tmax = k_cache.size(1);
+  TORCH_CHECK(v_cache.size(1) == Tmax, "dlion kv_append_chunk: the caches differ in length");
+  TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == at::kInt && pos.is_contiguous() && pos.numel() == B,
+              "dlion kv_append_chunk: pos must be a contiguous int32 [B] GPU tensor");
+  const int* nn = chunk_n_new("kv_append_chunk", n_new, B);
+  TORCH_CHECK(err.is_cuda() && err.scalar_type() == at::kInt && err.numel() >= 1,
+              "dlion kv_append_chunk: err must be int32[1]");
+  TORCH_CHECK(cos.has_value() == sin.has_value() && q_gamma.has_value() == k_gamma.has_value() &&
+                  (!q_gamma.has_value() || cos.has_value()),
+              "dlion kv_append_chunk: cos / sin and q_gamma / k_gamma come as pairs, gains only with tables");
+  if (cos.has_value())
+    for (const Tensor* t : {&*cos, &*sin})
+      TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kBFloat16 && t->is_contiguous() && t->dim() == 2 &&
+                      t->size(0) >= Tmax && t->size(1) == D && reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                  "dlion kv_append_chunk: cos/sin must be contiguous bf16 [>= Tmax, D]");
+  if (q_gamma.has_value())
+    for (const Tensor* g : {&*q_gamma, &*k_gamma})
+      TORCH_CHECK(g->is_cuda() && g->scalar_type() == at::kBFloat16 && g->is_contiguous() && g->numel() == D &&
+                      reinterpret_cast<uintptr_t>(g->data_ptr()) % 16 == 0,
+                  "dlion kv_append_chunk: gains must be contiguous, 16-byte aligned bf16 [D]");
+  const c10::DeviceGuard dg(q.device());
+  auto q_out = at::empty({B, T, H, D}, q.options());
+  check_hip(dlion::launch_kv_append_chunk(
+                q.data_ptr(), k.data_ptr(), v.data_ptr(), chunk_batch_stride(q), chunk_token_stride(q),
+                chunk_batch_stride(k), chunk_token_stride(k), chunk_batch_stride(v), chunk_token_stride(v),
+                pos.data_ptr<int>(), nn, cos.has_value() ? cos->data_ptr() : nullptr,
+                sin.has_value() ? sin->data_ptr() : nullptr, q_gamma.has_value() ? q_gamma->data_ptr() : nullptr,
+                k_gamma.has_value() ? k_gamma->data_ptr() : nullptr, static_cast<float>(eps), q_out.data_ptr(),
+                k_cache.data_ptr(), v_cache.data_ptr(), cache_batch_stride(k_cache), cache_token_stride(k_cache),
+                cache_batch_stride(v_cache), cache_token_stride(v_cache), static_cast<int>(B), static_cast<int>(T),
+                static_cast<int>(H), static_cast<int>(Hkv), static_cast<int>(D), static_cast<int>(Tmax),
+                err.data_ptr<int>(), cur_stream()),
+            "kv_append_chunk");
+  return q_out;
+}
+
+// out [B, T, H D]; splits / chunk from ops/fused.py chunk_splits (a host rule over B, Hkv, max_len, T, window only)
+Tensor chunk_attention(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const Tensor& kv_len,
+                       const std::optional<Tensor>& n_new, int64_t window, int64_t max_len, int64_t splits,
+                       int64_t chunk) {
+  TORCH_CHECK(q.dim() == 4 && k_cache.dim() == 4,
+              "dlion chunk_attention: q must be [B, T, H, D], the caches [B, Tmax, Hkv, D]");
+  const int64_t B = q.size(0), T = q.size(1), H = q.size(2), D = q.size(3), Tmax = k_cache.size(1), Hkv = k_cache.size(2);
+  TORCH_CHECK(D == 64 || D == 128, "dlion chunk_attention: head_dim must be 64 or 128");
+  TORCH_CHECK(T >= 1 && T <= dlion::kChunkMaxTokens, "dlion chunk_attention: T must be in [1, 8]");
+  TORCH_CHECK(Hkv >= 1 && H % Hkv == 0 && H / Hkv <= 8, "dlion chunk_attention: H / Hkv must be an integer in [1, 8]");
+  TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16 && q.is_contiguous() &&
+                  reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0,
+              "dlion chunk_attention: q must be a contiguous, 16-byte aligned bf16 GPU tensor");
+  check_cache("chunk_attention", "k_cache", k_cache, B, Hkv, D);
+  check_cache("chunk_attention", "v_cache", v_cache, B, Hkv, D);
+  TORCH_CHECK(v_cache.size(1) == Tmax, "dlion chunk_attention: the caches differ in length");
+  TORCH_CHECK(kv_len.is_cuda() && kv_len.scalar_type() == at::kInt && kv_len.is_contiguous() && kv_len.numel() == B,
+              "dlion chunk_attention: kv_len must be a contiguous int32 [B] GPU tensor");
+  const int* nn = chunk_n_new("chunk_attention", n_new, B);
+  TORCH_CHECK(max_len >= 1 && max_len < (int64_t{1} << 31) && window >= 0 && window < (int64_t{1} << 30) &&
+                  splits >= 1 && splits <= dlion::kDecodeMaxSplits && chunk >= 1 && chunk < (int64_t{1} << 31) &&
+                  B <= 65535 && Hkv <= 65535,
+              "dlion chunk_attention: bad max_len / window / splits / chunk / batch");
+  const c10::DeviceGuard dg(q.device());
+  const auto f32 = q.options().dtype(at::kFloat);
+  auto part_ml = at::empty({2, B, T, H, splits}, f32);
+  auto part_o = at::empty({B, T, H, splits, D}, f32);
+  auto out = at::empty({B, T, H * D}, q.options());
+  float* pm = part_ml.data_ptr<float>();
+  check_hip(dlion::launch_chunk_attention(
+                q.data_ptr(), k_cache.data_ptr(), cache_batch_stride(k_cache), cache_token_stride(k_cache),
+                v_cache.data_ptr(), cache_batch_stride(v_cache), cache_token_stride(v_cache), kv_len.data_ptr<int>(), nn,
+                pm, pm + B * T * H * splits, part_o.data_ptr<float>(), out.data_ptr(), static_cast<int>(B),
+                static_cast<int>(T), static_cast<int>(H), static_cast<int>(Hkv), static_cast<int>(D),
+                static_cast<int>(Tmax), static_cast<int>(max_len), static_cast<int>(window), static_cast<int>(splits),
+                static_cast<int>(chunk), 1.0f / std::sqrt(static_cast<float>(D)), cur_stream()),
+            "chunk_attention");
+  return out;
+}
 // ---- decode projections (csrc/skinny_gemm.hip)
 // the operands both forms share: x [M, K] bf16 rows (unit inner stride, 16-byte aligned base and row stride), out a
 // row-major bf16 [M, N] view with its own leading dimension, bias contiguous bf16 [N]; (splits, per) from
@@ -1554,6 +1669,10 @@ TORCH_LIBRARY(dlion, m) {
         " float eps, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor(c!) err) -> Tensor");
   m.def("decode_attention(Tensor q, Tensor k_cache, Tensor v_cache, Tensor kv_len, int window, int max_len, int splits,"
         " int chunk) -> Tensor");
+  m.def("kv_append_chunk(Tensor q, Tensor k, Tensor v, Tensor pos, Tensor? n_new, Tensor? cos, Tensor? sin,"
+        " Tensor? q_gamma, Tensor? k_gamma, float eps, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor(c!) err) -> Tensor");
+  m.def("chunk_attention(Tensor q, Tensor k_cache, Tensor v_cache, Tensor kv_len, Tensor? n_new, int window,"
+        " int max_len, int splits, int chunk) -> Tensor");
   m.def("quant4(Tensor w, Tensor code) -> (Tensor, Tensor)");
   m.def("dequant4_(Tensor q, Tensor absmax, Tensor code, Tensor(a!) out) -> ()");
   m.def("gemm_tn(Tensor[] P, Tensor[] Q, int splits) -> Tensor");
@@ -1692,6 +1811,8 @@ TORCH_LIBRARY_IMPL(dlion, CUDA, m) {
   m.impl("transpose_pad", &transpose_pad);
   m.impl("kv_append", &kv_append);
   m.impl("decode_attention", &decode_attention);
+  m.impl("kv_append_chunk", &kv_append_chunk);
+  m.impl("chunk_attention", &chunk_attention);
   m.impl("skinny_gemm_nt", &skinny_gemm_nt);
   m.impl("skinny_gemm_w4", &skinny_gemm_w4);
 }

@@ -201,6 +201,29 @@ hipError_t launch_decode_attention(const void* q, int64_t q_ld, const void* k_ca
                                    float* part_l, float* part_o, void* out, int B, int H, int Hkv, int D, int Tmax,
                                    int max_len, int window, int splits, int chunk, float scale, hipStream_t st);
 
+// ---- generation, T tokens per sequence (chunk_attention.hip); bf16, D in {64, 128}, 1 <= T <= kChunkMaxTokens
+// kv_append over a chunk: q [B, T, H, D] / k / v [B, T, Hkv, D] (batch / token strides *_bs / *_ts, heads
+// contiguous); token t of row b is normed / rotated at pos[b] + t and k, v written to cache[b, pos[b] + t] when
+// t < n_new[b] (n_new nullable: T for every row, else clamped into [0, T]); a written token outside [0, Tmax)
+// ORs kIndexErrCache into err[0] and is not written.  q_out [B, T, H, D] is written for every token.
+constexpr int kChunkMaxTokens = 8;
+hipError_t launch_kv_append_chunk(const void* q, const void* k, const void* v, int64_t q_bs, int64_t q_ts,
+                                  int64_t k_bs, int64_t k_ts, int64_t v_bs, int64_t v_ts, const int* pos,
+                                  const int* n_new, const void* cos, const void* sin, const void* q_gamma,
+                                  const void* k_gamma, float eps, void* q_out, void* k_cache, void* v_cache,
+                                  int64_t kc_bs, int64_t kc_ts, int64_t vc_bs, int64_t vc_ts, int B, int T, int H,
+                                  int Hkv, int D, int Tmax, int32_t* err, hipStream_t st);
+// out [B, T, H D]: query (b, t), t < n_new[b], attends the keys [max(0, len + t + 1 - window), len + t + 1) of
+// its cache, len = kv_len[b] (the length before the chunk; len + n_new is clamped to min(max_len, Tmax)); other
+// queries give zero rows.  q [B, T, H, D] contiguous.  splits blocks of chunk keys per (kv head, row), splits
+// chunk >= min(window + T - 1, max_len); fp32 partials part_m / part_l [B, T, H, splits], part_o [B, T, H,
+// splits, D], reduced by a combine pass.
+hipError_t launch_chunk_attention(const void* q, const void* k_cache, int64_t k_bs, int64_t k_ts,
+                                  const void* v_cache, int64_t v_bs, int64_t v_ts, const int* kv_len,
+                                  const int* n_new, float* part_m, float* part_l, float* part_o, void* out, int B,
+                                  int T, int H, int Hkv, int D, int Tmax, int max_len, int window, int splits,
+                                  int chunk, float scale, hipStream_t st);
+
 // ---- decode projections (skinny_gemm.hip); bf16, 1 <= M <= 16, K % 64 == 0, any N
 // out[M, N] (row stride ldo) = x[M, K] (row stride ldx, 16-byte aligned rows) . w[N, K]^T (+ bias[N]), fp32
 // accumulation, one rounding.  The 128-k steps of K are cut into `splits` runs of `per` steps ((splits - 1) per <

@@ -4,13 +4,16 @@
 k and v in, so the prefill writes them with plain copies -- and the per-row lengths on the device.  The models
 take it as an optional ``cache`` argument (models/llama.py, models/gpt2.py): the first call is the prefill (the
 prompt through the flash forward), every later call one decode step (one token per row through
-``fused.kv_append`` and ``fused.decode_attention``, csrc/decode.hip).
+``fused.kv_append`` and ``fused.decode_attention``, csrc/decode.hip) or a chunk of up to 8 tokens per row, ragged
+by ``n_new`` (``fused.kv_append_chunk`` and ``fused.chunk_attention``, csrc/chunk_attention.hip);
+``KVCache.truncate`` rolls rows back.
 
 ``NativeGenerateMixin.generate`` uses HF's argument names: greedy or sampled (temperature, then top-k, then
 top-p), ragged prompts by ``attention_mask`` (left- or right-padded), EOS / pad handling; ``num_beams > 1`` is beam
-search (HF's semantics) on ``fused.lm_head_topk``.  Out of scope: beam sampling, diverse / constrained beams,
-repetition penalties, a paged or rolling cache (a windowed layer keeps its full-length cache and only
-bounds the key range), graph capture, speculative decoding.
+search (HF's semantics) on ``fused.lm_head_topk``; ``assistant_model`` is greedy speculative decoding (a draft
+model proposes, one chunk forward of this model checks).  Out of scope: beam sampling, diverse / constrained
+beams, repetition penalties, a paged or rolling cache (a windowed layer keeps its full-length cache and only
+bounds the key range), graph capture, speculative sampling.
 """
 from __future__ import annotations
 
@@ -30,6 +33,16 @@ class GenerateOutput(NamedTuple):
 
     sequences: torch.Tensor
     sequences_scores: Optional[torch.Tensor]
+
+
+class SpeculativeOutput(NamedTuple):
+    """``generate(..., assistant_model=m, return_dict_in_generate=True)``: ``sequences`` as without an assistant,
+    ``rounds`` (int: draft + verify rounds run) and ``accepted`` [rows]: the draft tokens each row accepted."""
+
+    sequences: torch.Tensor
+    sequences_scores: Optional[torch.Tensor]
+    rounds: int
+    accepted: torch.Tensor
 
 
 def cache_geometry(config):
@@ -56,35 +69,66 @@ class KVCache:
         self.kv_len = self.lengths  # lengths + 1 during a decode step
         self.width = 0
         self.prefilled = False
+        self.chunk = False  # the forward in flight takes the chunk path (T > 1 tokens per row, or ragged)
+        self.n_new = None  # int32 [B]: the tokens of the chunk in flight that row b keeps (None: all T)
 
     def layer(self, i: int):
         """(k, v) of layer i, each [B, max_len, Hkv, D]."""
         return self._buf[i, 0], self._buf[i, 1]
 
-    def begin(self, B: int, T: int) -> bool:
-        """Start a forward of T tokens per row; True for the prefill (the first call)."""
+    def begin(self, B: int, T: int, n_new: Optional[torch.Tensor] = None) -> bool:
+        """Start a forward of T tokens per row; True for the prefill (the first call).  After the prefill T = 1
+        is a decode step and 1 < T <= 8 a chunk (``fused.kv_append_chunk`` / ``fused.chunk_attention``), of
+        which row b keeps the first ``n_new[b]`` tokens ([B], 0 <= n_new[b] <= T; None: all T)."""
         if B != self.batch:
             raise ValueError(f"KVCache: built for batch {self.batch}, got {B}")
         if torch.is_grad_enabled():
             raise RuntimeError("KVCache: the cached forward is inference only; call it under torch.no_grad()")
         if not self.prefilled:
+            if n_new is not None:
+                raise ValueError("KVCache: n_new belongs to a chunk after the prefill (ragged prompts: set_lengths)")
             if T > self.max_len:
                 raise ValueError(f"KVCache: a prompt of {T} tokens does not fit max_len {self.max_len}")
             return True
-        if T != 1:
-            raise ValueError("KVCache: after the prefill a forward takes one token per row")
-        if self.width + 1 > self.max_len:
+        if not 1 <= T <= fused.CHUNK_MAX_TOKENS:
+            raise ValueError(f"KVCache: after the prefill a forward takes 1 to {fused.CHUNK_MAX_TOKENS} tokens per row")
+        if self.width + T > self.max_len:
             raise ValueError(f"KVCache: full ({self.max_len} positions)")
-        self.kv_len = self.lengths + 1
+        self.chunk = T > 1 or n_new is not None
+        if self.chunk:
+            if n_new is not None and tuple(n_new.shape) != (B,):
+                raise ValueError("KVCache: n_new must be [B]")
+            self.n_new = None if n_new is None else n_new.to(device=self.lengths.device, dtype=torch.int32)
+            self.kv_len = self.lengths  # the chunk ops take the lengths before the chunk
+        else:
+            self.kv_len = self.lengths + 1
         return False
 
     def advance(self, T: int) -> None:
         if not self.prefilled:
             self.lengths.fill_(T)
             self.width, self.prefilled = T, True
+        elif self.chunk:
+            if self.n_new is None:
+                self.lengths += T
+            else:
+                self.lengths += self.n_new.clamp(0, T)
+            self.width += T
+            self.chunk, self.n_new = False, None
         else:
             self.lengths += 1
             self.width += 1
+
+    def truncate(self, lengths: torch.Tensor, width: int) -> None:
+        """Roll rows back (speculative decoding: rejected drafts): row b now holds ``lengths[b]`` tokens, not more
+        than it did, and ``width`` is the caller's host bound on them.  No data moves: nothing at or beyond a
+        row's length is ever read, and the next forward overwrites it."""
+        width = int(width)
+        if not self.prefilled or not 0 <= width <= self.width:
+            raise ValueError(f"KVCache.truncate: width must be in [0, {self.width}] of a prefilled cache")
+        self.lengths.copy_(lengths.to(self.lengths.dtype))
+        self.kv_len = self.lengths
+        self.width = width
 
     def set_lengths(self, lengths: torch.Tensor) -> None:
         """Ragged prompts, left-aligned in the prefill: row b holds ``lengths[b]`` <= width real tokens."""
@@ -106,6 +150,7 @@ class KVCache:
         out.lengths = self.lengths.repeat_interleave(n)
         out.kv_len = out.lengths
         out.width, out.prefilled = self.width, self.prefilled
+        out.chunk, out.n_new = False, None
         return out
 
     def reorder_rows(self, index: torch.Tensor, lo: int = 0) -> None:
@@ -173,7 +218,8 @@ class NativeGenerateMixin:
                  max_new_tokens: int = 20, do_sample: bool = False, temperature: float = 1.0, top_k: int = 0,
                  top_p: float = 1.0, eos_token_id=None, pad_token_id: Optional[int] = None,
                  seed: Optional[int] = None, num_beams: int = 1, num_return_sequences: int = 1,
-                 length_penalty: float = 1.0, early_stopping: bool = False, return_dict_in_generate: bool = False):
+                 length_penalty: float = 1.0, early_stopping: bool = False, return_dict_in_generate: bool = False,
+                 assistant_model=None, num_assistant_tokens: int = 5):
         """[B, T0] prompts -> [B, T0 + n_new] long: the prompt exactly as given, then the new tokens.
 
         Greedy takes the top-1 of ``fused.lm_head_score`` (the lowest id on ties, no [B, V] tensor); sampling
@@ -187,7 +233,14 @@ class NativeGenerateMixin:
         T0 + n_new]), ``length_penalty`` and ``early_stopping`` (False or True) as there; every step takes the
         ``max(2, 1 + #eos) * num_beams`` best continuations of every live beam from ``fused.lm_head_topk``.
         ``return_dict_in_generate=True`` returns :class:`GenerateOutput` (``sequences``, ``sequences_scores``; the
-        scores are None without beams)."""
+        scores are None without beams).
+
+        ``assistant_model`` (a native causal LM with the same vocabulary size) turns greedy decoding into greedy
+        speculative decoding: per round the assistant drafts up to ``num_assistant_tokens`` (1..7) tokens with
+        single-token steps and this model checks them in one chunk forward (``fused.chunk_attention``), keeping
+        the longest prefix it agrees with plus its own next token -- the tokens plain greedy decoding produces,
+        for fewer passes over this model's weights.  ``return_dict_in_generate=True`` then returns
+        :class:`SpeculativeOutput`."""
         num_beams, num_return_sequences = int(num_beams), int(num_return_sequences)
         if num_beams < 1:
             raise ValueError("generate: num_beams must be >= 1")
@@ -221,8 +274,30 @@ class NativeGenerateMixin:
             eos = torch.as_tensor([eos_token_id] if isinstance(eos_token_id, int) else list(eos_token_id), device=dev)
             if pad_token_id is None:
                 pad_token_id = int(eos[0])
+        if assistant_model is not None:
+            if do_sample or num_beams != 1:
+                raise ValueError("generate: assistant_model is greedy speculative decoding; it needs do_sample=False "
+                                 "and num_beams=1 (speculative sampling and assisted beam search are not supported)")
+            k = int(num_assistant_tokens)
+            if not 1 <= k <= fused.CHUNK_MAX_TOKENS - 1:
+                raise ValueError(f"generate: num_assistant_tokens must be in [1, {fused.CHUNK_MAX_TOKENS - 1}] (the "
+                                 f"target checks the drafts and one more token in a chunk of at most "
+                                 f"{fused.CHUNK_MAX_TOKENS}), got {num_assistant_tokens}")
+            acfg = assistant_model.config
+            if acfg.vocab_size != cfg.vocab_size:
+                raise ValueError(f"generate: the assistant's vocabulary ({acfg.vocab_size}) differs from the "
+                                 f"model's ({cfg.vocab_size})")
+            if assistant_model.training:
+                raise ValueError("generate: the assistant model is in training mode; call assistant_model.eval() first")
+            if acfg.model_type == "gpt2" and total > acfg.n_positions:
+                raise ValueError(f"generate: {T0} prompt + {max_new_tokens} new tokens exceed the assistant's "
+                                 f"{acfg.n_positions} learned positions")
         ids, lens = left_align(input_ids, attention_mask)
         weight = self.lm_head.weight
+        if assistant_model is not None:
+            out = self._speculative(assistant_model, input_ids, ids, lens, max_new_tokens, eos, pad_token_id, k)
+            fused.check_index_errors()
+            return out if return_dict_in_generate else out.sequences
         if num_beams > 1:
             lo = T0 if attention_mask is None else int(lens.min())
             out = self._beam_search(input_ids, ids, lens, lo, max_new_tokens, eos, pad_token_id, num_beams,
@@ -268,6 +343,98 @@ class NativeGenerateMixin:
         fused.check_index_errors()
         out = torch.cat([input_ids, new[:, :n_new]], dim=1)
         return GenerateOutput(out, None) if return_dict_in_generate else out
+
+    def _speculative(self, assistant, input_ids, ids, lens, n, eos, pad_token_id, k):
+        """Greedy speculative decoding.  Row b has emitted ``count[b]`` tokens, the last of which (``last``) is not
+        in the target's cache yet; the assistant's cache lacks the last one or two of them (``unseen``: two when
+        every draft of the previous round was accepted, since the last draft was never fed to the assistant).  A
+        round: the assistant absorbs ``unseen`` in a ragged chunk of 2 and drafts kk tokens (kk - 1 single-token
+        steps), the target runs one chunk of ``last`` and the drafts, row b keeps the ``a[b]`` drafts that equal the
+        target's top-1 and the target's next token, and both caches are rolled back to what stays valid.  Rows
+        that have emitted EOS or all n tokens are parked at length 0 (their forwards go on, unread).  One host
+        read per round: whether a row is still open, and the caches' widths."""
+        B, T0 = input_ids.shape
+        dev = input_ids.device
+        cfg, weight, base = self.config, self.lm_head.weight, self._decoder()
+        acfg, a_weight, a_base = assistant.config, assistant.lm_head.weight, assistant._decoder()
+        size = T0 + n + k + 1  # the last round may run k + 1 positions past the last kept token
+        limit_t = min(size, cfg.n_positions) if cfg.model_type == "gpt2" else size
+        limit_a = min(size, acfg.n_positions) if acfg.model_type == "gpt2" else size
+        rows = torch.arange(B, device=dev)
+        cache = KVCache(cfg, B, size, dev, weight.dtype)
+        a_cache = KVCache(acfg, B, size, dev, a_weight.dtype)
+        h = base(ids, cache=cache)[rows, lens - 1]
+        cache.set_lengths(lens)
+        a_base(ids, cache=a_cache)
+        a_cache.set_lengths(lens)
+
+        def top1(hidden, w):
+            flat = hidden.reshape(-1, hidden.shape[-1])
+            return fused.lm_head_score(flat, w, torch.full((flat.shape[0],), -100, dtype=torch.long, device=dev)).pred.long()
+
+        new = torch.zeros(B, n + k + 1, dtype=torch.long, device=dev)
+        last = top1(h, weight)
+        new[:, 0] = last
+        count = torch.ones(B, dtype=torch.long, device=dev)
+        accepted = torch.zeros(B, dtype=torch.long, device=dev)
+        finished = torch.isin(last, eos) if eos is not None else torch.zeros(B, dtype=torch.bool, device=dev)
+        active = ~finished & (count < n)
+        t_len, a_len = lens.clone(), lens.clone()  # the caches' lengths (long)
+        unseen = torch.stack([last, last], dim=1)
+        n_unseen = torch.ones(B, dtype=torch.long, device=dev)
+        rounds = 0
+        t_width = a_width = T0
+        go_on = n > 1 and bool(active.any())
+        if go_on and not bool(active.all()):
+            t_len, a_len, n_unseen = t_len * active, a_len * active, n_unseen * active
+            cache.truncate(t_len, t_width)
+            a_cache.truncate(a_len, a_width)
+        while go_on:
+            kk = min(k, limit_t - t_width - 1, limit_a - a_width - 1)  # >= 1: an open row has room for 2 more tokens
+            rounds += 1
+            # the assistant: absorb the accepted tokens it has not seen, then draft
+            ha = a_base(unseen, cache=a_cache, n_new=n_unseen.to(torch.int32))
+            drafts = [top1(ha[rows, (n_unseen - 1).clamp_min(0)], a_weight)]
+            for _ in range(kk - 1):
+                drafts.append(top1(a_base(drafts[-1][:, None], cache=a_cache)[:, 0], a_weight))
+            drafts = torch.stack(drafts, dim=1)  # [B, kk]
+            # the target: one chunk over the last emitted token and the drafts
+            chunk = torch.cat([last[:, None], drafts], dim=1)
+            pred = top1(base(chunk, cache=cache), weight).view(B, kk + 1)  # the target's token after each of the chunk's inputs
+            a = (pred[:, :kk] == drafts).long().cumprod(1).sum(1)  # accepted drafts
+            adv = torch.where(active, torch.minimum(a + 1, n - count), torch.zeros_like(a))
+            step = torch.arange(kk + 1, device=dev)
+            keep = step[None, :] < adv[:, None]
+            at = (count[:, None] + step[None, :]).clamp_max(new.shape[1] - 1)
+            new.scatter_(1, at, torch.where(keep, pred, new.gather(1, at)))
+            if eos is not None:
+                finished = finished | (keep & torch.isin(pred, eos)).any(1)
+            accepted += torch.minimum(a, adv)
+            count = count + adv
+            last = torch.where(adv > 0, pred.gather(1, (adv - 1).clamp_min(0)[:, None])[:, 0], last)
+            active = active & ~finished & (count < n)
+            # roll back: the target keeps `last` and the accepted drafts, the assistant what it was fed of them
+            full = adv == kk + 1
+            fed = torch.minimum(adv - 1, torch.full_like(adv, kk - 1)).clamp_min(0)
+            t_len = (t_len + adv) * active
+            a_len = (a_len + n_unseen + fed) * active
+            n_unseen = torch.where(full, 2, 1) * active
+            unseen = torch.stack([torch.where(full, drafts[:, kk - 1], last), last], dim=1)
+            state = torch.stack([active.any().long(), t_len.max(), a_len.max()]).tolist()  # the round's host read
+            go_on, t_width, a_width = bool(state[0]), int(state[1]), int(state[2])
+            cache.truncate(t_len, t_width)
+            a_cache.truncate(a_len, a_width)
+        n_out = n
+        new = new[:, :n]
+        if eos is not None:
+            step = torch.arange(n, device=dev)
+            first = torch.where(torch.isin(new, eos), step[None, :], torch.full_like(new, n)).min(1).values
+            new = torch.where(step[None, :] > first[:, None], torch.full_like(new, pad_token_id), new)
+            done = int(first.max())
+            if done < n:
+                n_out = done + 1
+        out = torch.cat([input_ids, new[:, :n_out]], dim=1)
+        return SpeculativeOutput(out, None, rounds, accepted)
 
     def _beam_search(self, input_ids, ids, lens, lo, n, eos, pad_token_id, nb, n_ret, length_penalty, early_stopping):
         """transformers' ``GenerationMixin._beam_search`` on the native cache: the same running / finished beam

@@ -87,11 +87,15 @@ class Attention(nn.Module):
     def _attend_cached(self, x, cache):
         """Generation (models/generation.py KVCache): the packed qkv split into its q | k | v column views.
         Prefill: k and v copied into cache[:, :T], attention by the flash forward.  Decode step: a pure append
-        (no rotary tables) and fused.decode_attention over the cache."""
+        (no rotary tables) and fused.decode_attention over the cache; a chunk of T tokens per row: their chunk forms."""
         B, T, C = x.shape
         H, D = self.n_head, self.head_dim
         kc, vc = cache.layer(self.layer_idx)
         qkv = self.c_attn(x)
+        if cache.prefilled and cache.chunk:
+            q, k, v = (qkv[..., j * C:(j + 1) * C].view(B, T, H, D) for j in range(3))
+            q = fused.kv_append_chunk(q, k, v, cache.lengths, None, None, None, None, 0.0, kc, vc, cache.n_new)
+            return fused.chunk_attention(q, kc, vc, cache.kv_len, cache.n_new, 0, cache.width + T)
         if cache.prefilled:
             q, k, v = (qkv[:, 0, j * C:(j + 1) * C].view(B, H, D) for j in range(3))
             q = fused.kv_append(q, k, v, cache.lengths, None, None, None, None, 0.0, kc, vc)
@@ -154,9 +158,9 @@ class GPT2Model(nn.Module):
         self.embd_pdrop = cfg.embd_pdrop
         self.gradient_checkpointing = False
 
-    def forward(self, input_ids, cache=None):
+    def forward(self, input_ids, cache=None, n_new=None):
         if cache is not None:
-            return self._forward_cached(input_ids, cache)
+            return self._forward_cached(input_ids, cache, n_new)
         p = self.embd_pdrop if self.training else 0.0
         x = fused.embed(input_ids, self.wte.weight, self.wpe.weight, p)  # gather + add + dropout, one kernel
         if self.gradient_checkpointing and self.training:
@@ -177,12 +181,16 @@ class GPT2Model(nn.Module):
                                           bias=blk.mlp.c_proj.bias)
         return h
 
-    def _forward_cached(self, input_ids, cache):
-        """The prefill (first call on a fresh KVCache: the whole prompt) or one decode step (one token per
-        row, at position lengths[b]) of generation, through the fused chain of ``forward`` without dropout."""
+    def _forward_cached(self, input_ids, cache, n_new=None):
+        """The prefill (first call on a fresh KVCache: the whole prompt), one decode step (one token per row, at
+        position lengths[b]) or a chunk (up to 8 tokens per row at the positions lengths[b] + t, of which row b
+        keeps ``n_new[b]``) of generation, through the fused chain of ``forward`` without dropout."""
         B, T = input_ids.shape
-        if cache.begin(B, T):
+        if cache.begin(B, T, n_new):
             x = fused.embed(input_ids, self.wte.weight, self.wpe.weight, 0.0)
+        elif cache.chunk:
+            pos = fused.chunk_positions(cache.lengths, T, cache.n_new, self.wpe.weight.shape[0])
+            x = F.embedding(input_ids, self.wte.weight) + F.embedding(pos, self.wpe.weight)
         else:
             x = F.embedding(input_ids, self.wte.weight) + F.embedding(cache.lengths.long(), self.wpe.weight)[:, None]
         first = self.h[0].ln_1

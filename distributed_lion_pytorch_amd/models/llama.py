@@ -203,6 +203,14 @@ class LlamaAttention(nn.Module):
         kc, vc = cache.layer(self.layer_idx)
         q, k, v = _proj(x, (self.q_proj, self.k_proj, self.v_proj))
         gq, gk, eps = (self.q_norm.weight, self.k_norm.weight, self.q_norm.eps) if hasattr(self, "q_norm") else (None, None, 0.0)
+        if cache.prefilled and cache.chunk:
+            # T tokens per row (1 < T <= 8, or ragged): token t at position lengths[b] + t, causal inside the chunk
+            q = q.view(B, T, self.n_head, self.head_dim)
+            k = k.view(B, T, self.n_kv, self.head_dim)
+            v = v.view(B, T, self.n_kv, self.head_dim)
+            q = fused.kv_append_chunk(q, k, v, cache.lengths, cos, sin, gq, gk, eps, kc, vc, cache.n_new)
+            y = fused.chunk_attention(q, kc, vc, cache.kv_len, cache.n_new, self.window, cache.width + T)
+            return _lin(self.o_proj, y)
         if cache.prefilled:
             q = q[:, 0].view(B, self.n_head, self.head_dim)
             k = k[:, 0].view(B, self.n_kv, self.head_dim)
@@ -311,9 +319,9 @@ class LlamaModel(nn.Module):
                 per_window[w] = fused.visibility_bounds(position_ids, w)
         return [per_window[layer.self_attn.window] for layer in self.layers]
 
-    def forward(self, input_ids, position_ids=None, cache=None):
+    def forward(self, input_ids, position_ids=None, cache=None, n_new=None):
         if cache is not None:
-            return self._forward_cached(input_ids, cache)
+            return self._forward_cached(input_ids, cache, n_new)
         T = input_ids.shape[1]
         x = self.embed_tokens(input_ids)
         # position_ids that restart per document (packed rows) bound every row's
@@ -339,11 +347,12 @@ class LlamaModel(nn.Module):
             x, h = fused.dropout_add_norm(layer.mlp(h), x, nxt.weight, None, nxt.eps, 0.0, rms=True)
         return h
 
-    def _forward_cached(self, input_ids, cache):
-        """The prefill (first call on a fresh KVCache: the whole prompt) or one decode step (one token per
-        row) of generation: the fused residual + norm chain of ``forward`` with the layers' cached attention."""
+    def _forward_cached(self, input_ids, cache, n_new=None):
+        """The prefill (first call on a fresh KVCache: the whole prompt), one decode step (one token per row) or
+        a chunk (up to 8 tokens per row, of which row b keeps ``n_new[b]``) of generation: the fused residual +
+        norm chain of ``forward`` with the layers' cached attention."""
         B, T = input_ids.shape
-        cache.begin(B, T)
+        cache.begin(B, T, n_new)
         x = self.embed_tokens(input_ids)
         cos, sin = self.rotary.tables(cache.max_len, x.device, x.dtype)
         first = self.layers[0].input_layernorm

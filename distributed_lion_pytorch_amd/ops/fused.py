@@ -1290,6 +1290,162 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
     return decode_attention_reference(q, k_cache, v_cache, kv_len, window, max_len)
 
 
+# T tokens per sequence against the cache (csrc/chunk_attention.hip): speculative decoding's verification forward.
+CHUNK_MAX_TOKENS = 8  # csrc/kernels.h kChunkMaxTokens
+
+
+def chunk_splits(B: int, Hkv: int, max_len: int, T: int, window: int = 0, splits=None):
+    """(splits, chunk) of the chunk-attention grid: ``decode_splits`` over the keys a row's T queries span, at
+    most ``max_len`` (the host bound on kv_len + T) and ``window + T - 1`` under a window."""
+    return decode_splits(B, Hkv, max_len, int(window) + T - 1 if window else 0, splits)
+
+
+def _chunk_rows_ok(x: torch.Tensor) -> bool:
+    """[B, T, heads, D] with contiguous heads and 16-byte aligned token / batch strides (a column view of a
+    fused q|k|v projection output)."""
+    B, T, Hx, D = x.shape
+    ts = x.stride(1) if T > 1 else Hx * D
+    return (x.stride(3) == 1 and (Hx == 1 or x.stride(2) == D) and x.data_ptr() % 16 == 0
+            and (T == 1 or (ts % 8 == 0 and ts >= Hx * D)) and (B == 1 or (x.stride(0) % 8 == 0 and x.stride(0) >= T * ts)))
+
+
+def _chunk_counts(n_new, T: int, like: torch.Tensor) -> torch.Tensor:
+    if n_new is None:
+        return torch.full_like(like, T, dtype=torch.long)
+    return n_new.long().clamp(0, T)
+
+
+def chunk_positions(lengths: torch.Tensor, T: int, n_new, limit: int) -> torch.Tensor:
+    """Positions ``lengths[b] + t`` [B, T] (long) of a chunk's tokens, clamped into [0, limit) (a table of learned
+    positions); a token ``t < n_new[b]`` beyond the table raises through check_index_errors (on the CPU: at once)."""
+    t = torch.arange(T, device=lengths.device)
+    p = lengths.long()[:, None] + t[None, :]
+    bad = ((p >= limit) & (t[None, :] < _chunk_counts(n_new, T, lengths)[:, None])).any()
+    if p.is_cuda:
+        _index_flag(p.device).bitwise_or_(bad.to(torch.int32) * _IDX_CACHE)
+    elif bool(bad):
+        raise _index_error(_IDX_CACHE, "chunk_positions")
+    return p.clamp(0, limit - 1)
+
+
+def kv_append_chunk_reference(q, k, v, pos, cos, sin, q_gamma, k_gamma, eps, k_cache, v_cache, n_new=None) -> torch.Tensor:
+    """The PyTorch form of kv_append_chunk (same arguments): rope_reference / qk_norm_rope_reference at the
+    positions pos[b] + t, then an indexed write of the tokens t < n_new[b] into cache[b, pos[b] + t]."""
+    B, T = q.shape[:2]
+    Tmax = k_cache.shape[1]
+    n = _chunk_counts(n_new, T, pos)
+    t = torch.arange(T, device=q.device)
+    p = pos.long()[:, None] + t[None, :]  # [B, T]
+    live = t[None, :] < n[:, None]
+    inside = (p >= 0) & (p < Tmax)
+    bad = (live & ~inside).any()
+    if p.is_cuda:
+        _index_flag(p.device).bitwise_or_(bad.to(torch.int32) * _IDX_CACHE)
+    elif bool(bad):
+        raise _index_error(_IDX_CACHE, "kv_append_chunk")
+    p = p.clamp(0, Tmax - 1)
+    if cos is not None:
+        c, s = cos[p][:, :, None, :], sin[p][:, :, None, :]  # [B, T, 1, D]
+        if q_gamma is not None:
+            def normed(x, gamma):
+                xf = x if x.dtype == torch.float64 else x.float()
+                return gamma * (xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps)).to(x.dtype)
+
+            q, k = normed(q, q_gamma), normed(k, k_gamma)
+        d2 = q.shape[-1] // 2
+
+        def rot(x):
+            return x * c + torch.cat([-x[..., d2:], x[..., :d2]], dim=-1) * s
+
+        q, k = rot(q), rot(k)
+    w = live & inside
+    rows = torch.arange(B, device=p.device)[:, None].expand(B, T)
+    k_cache[rows[w], p[w]] = k[w].to(k_cache.dtype)
+    v_cache[rows[w], p[w]] = v[w].to(v_cache.dtype)
+    return q.contiguous()
+
+
+def kv_append_chunk(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pos: torch.Tensor, cos, sin, q_gamma, k_gamma,
+                    eps: float, k_cache: torch.Tensor, v_cache: torch.Tensor, n_new=None) -> torch.Tensor:
+    """``kv_append`` for T tokens per row: q [B, T, H, D], k / v [B, T, Hkv, D] (column views of the fused q|k|v
+    output are read in place).  Token t of row b is normed / rotated at position ``pos[b] + t``; returns the
+    rotated q [B, T, H, D] and writes k and v of the tokens ``t < n_new[b]`` (int32 [B], clamped into [0, T];
+    None: all T) to ``cache[b, pos[b] + t]``.  The q rows of the other tokens are computed by the same
+    arithmetic and mean nothing.  A written position outside [0, Tmax) is not written and raises through
+    check_index_errors (on the CPU: at once).  The rotation and the norm are bit for bit those of ``rope`` /
+    ``qk_norm_rope`` at that position.  bf16 at head_dim 64 / 128 and T <= 8 runs csrc/chunk_attention.hip."""
+    if (cos is None) != (sin is None) or (q_gamma is None) != (k_gamma is None) or (q_gamma is not None and cos is None):
+        raise ValueError("kv_append_chunk: cos / sin and q_gamma / k_gamma come as pairs, gains only with tables")
+    T, D = q.shape[1], q.shape[-1]
+    Tmax = k_cache.shape[1]
+    if (q.dtype == k.dtype == v.dtype == torch.bfloat16 and D in (64, 128) and 1 <= T <= CHUNK_MAX_TOKENS and q.is_cuda
+            and pos.is_cuda and pos.dtype == torch.int32 and _cache_ok(k_cache) and _cache_ok(v_cache)
+            and (n_new is None or (n_new.is_cuda and n_new.dtype == torch.int32))
+            and all(t is None or (t.dtype == torch.bfloat16 and t.shape[0] >= Tmax) for t in (cos, sin))
+            and (q_gamma is None or all(g.dtype == torch.bfloat16 and g.is_contiguous() and g.data_ptr() % 16 == 0
+                                        for g in (q_gamma, k_gamma)))
+            and _use_hip(q)):
+        q, k, v = (t if _chunk_rows_ok(t) else t.contiguous() for t in (q, k, v))
+        if cos is not None:
+            cos, sin = cos.contiguous(), sin.contiguous()
+        return hip.ops().kv_append_chunk(q, k, v, pos.contiguous(), None if n_new is None else n_new.contiguous(), cos,
+                                         sin, q_gamma, k_gamma, float(eps), k_cache, v_cache, _index_flag(q.device))
+    return kv_append_chunk_reference(q, k, v, pos, cos, sin, q_gamma, k_gamma, eps, k_cache, v_cache, n_new)
+
+
+def chunk_attention_reference(q, k_cache, v_cache, kv_len, n_new=None, window: int = 0, max_len=None) -> torch.Tensor:
+    """The PyTorch form of chunk_attention (same arguments): masked softmax attention of T queries per sequence
+    in fp32 (fp64 inputs stay fp64).  Cache elements outside a query's key range are replaced by zeros before
+    they enter a product, so whatever they hold (NaN included) cannot reach the output."""
+    B, T, H, D = q.shape
+    Tmax, Hkv = k_cache.shape[1], k_cache.shape[2]
+    L = Tmax if max_len is None else max(1, min(int(max_len), Tmax))
+    base = kv_len.long().clamp(0, L)
+    n = torch.minimum(_chunk_counts(n_new, T, kv_len), L - base)
+    t = torch.arange(T, device=q.device)
+    top = base[:, None] + t[None, :] + 1  # [B, T]: one past the query's own key
+    j = torch.arange(L, device=q.device)
+    visible = (j[None, None, :] < top[:, :, None]) & (t[None, :] < n[:, None])[:, :, None]  # [B, T, L]
+    if window:
+        visible = visible & (j[None, None, :] >= (top - int(window))[:, :, None])
+    ct = torch.float64 if q.dtype == torch.float64 else torch.float32
+    zero = torch.zeros((), dtype=ct, device=q.device)
+    used = visible.any(1)  # [B, L]: keys some query of the row attends
+    kf = torch.where(used[:, :, None, None], k_cache[:, :L].to(ct), zero)
+    vf = torch.where(used[:, :, None, None], v_cache[:, :L].to(ct), zero)
+    qf = q.to(ct).reshape(B, T, Hkv, H // Hkv, D)
+    s = torch.einsum("btkgd,bjkd->btkgj", qf, kf) * (1.0 / D ** 0.5)
+    vis = visible[:, :, None, None, :]
+    s = s.masked_fill(~vis, float("-inf"))
+    P = torch.softmax(s, dim=-1)
+    P = torch.where(vis.any(-1, keepdim=True), P, zero)  # a query without keys: zeros, not 0 / 0
+    return torch.einsum("btkgj,bjkd->btkgd", P, vf).reshape(B, T, H * D).to(q.dtype)
+
+
+def chunk_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, kv_len: torch.Tensor, n_new=None,
+                    window: int = 0, max_len=None, splits=None) -> torch.Tensor:
+    """q [B, T, H, D] (T new queries per sequence, their keys already appended by ``kv_append_chunk``), caches
+    [B, Tmax, Hkv, D], kv_len int32 [B] (the lengths before the chunk) -> [B, T, H * D]: query (b, t) with
+    ``t < n_new[b]`` (int32 [B]; None: all T) attends the keys ``max(0, kv_len[b] + t + 1 - window) ..
+    kv_len[b] + t`` of its cache (``window`` 0: all of them), causal inside the chunk; the other queries give
+    zero rows.  ``max_len`` is a host bound on kv_len + T (default Tmax): it sizes the split grid without a
+    device sync, and kv_len + n_new is clamped to it.  bf16 at head_dim 64 / 128 with H / Hkv in 1..8 and
+    T <= 8 runs csrc/chunk_attention.hip (MFMA products, the split / partial / combine structure of
+    decode_attention, no atomics); anything else the PyTorch form.  ``splits`` forces the split count."""
+    B, T, H, D = q.shape
+    Tmax, Hkv = k_cache.shape[1], k_cache.shape[2]
+    window = int(window or 0)
+    max_len = Tmax if max_len is None else max(1, min(int(max_len), Tmax))
+    if (q.dtype == torch.bfloat16 and D in (64, 128) and 1 <= T <= CHUNK_MAX_TOKENS and H % Hkv == 0
+            and 1 <= H // Hkv <= 8 and q.is_cuda and kv_len.is_cuda and kv_len.dtype == torch.int32
+            and (n_new is None or (n_new.is_cuda and n_new.dtype == torch.int32)) and window < (1 << 30)
+            and _cache_ok(k_cache) and _cache_ok(v_cache) and B <= 65535 and Hkv <= 65535 and _use_hip(q)):
+        s, chunk = chunk_splits(B, Hkv, max_len, T, window, splits)
+        return hip.ops().chunk_attention(q.contiguous(), k_cache, v_cache, kv_len.contiguous(),
+                                         None if n_new is None else n_new.contiguous(), window, max_len, s, chunk)
+    return chunk_attention_reference(q, k_cache, v_cache, kv_len, n_new, window, max_len)
+
+
 # ------------------------------------------------- generation: the M <= 16 projections (csrc/skinny_gemm.hip)
 _SKINNY_STEP = 128  # k of one step of the kernel: the unit K is split in
 _SKINNY_CHUNK = 4  # steps a wave loads together: runs are whole chunks where K allows

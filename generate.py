@@ -8,6 +8,8 @@
     python generate.py --model_name_or_path gpt2 --prompt "The quick brown fox" --num_beams 4 --num_return_sequences 2
     python generate.py --model_name_or_path llama-2-7b --load_in_4bit --adapter ./sft/final_checkpoint \\
         --prompt "..." --bf16
+    python generate.py --model_name_or_path ./llama-8b --assistant_model ./llama-1b --num_assistant_tokens 5 \\
+        --prompt "..." --bf16
 
 ``--model_name_or_path`` is a named size (random weights, no hub access) or a local HF directory
 (models/registry.py); ``--adapter`` a peft-format LoRA directory as sft_llama2.py writes it.  A directory without a
@@ -46,6 +48,9 @@ def parse_args(argv=None):
     ap.add_argument("--num_return_sequences", type=int, default=1, help="beams returned per prompt, best first")
     ap.add_argument("--length_penalty", type=float, default=1.0)
     ap.add_argument("--early_stopping", action="store_true")
+    ap.add_argument("--assistant_model", default=None,
+                    help="a smaller model (name or directory) with the same vocabulary: greedy speculative decoding")
+    ap.add_argument("--num_assistant_tokens", type=int, default=5, help="draft tokens per round (1..7)")
     ap.add_argument("--bf16", action="store_true")
     ap.add_argument("--load_in_4bit", action="store_true",
                     help="keep the base model's linear layers in 4 bits (models/quant.py), as sft_llama2.py does")
@@ -80,6 +85,12 @@ def main(argv=None):
     if a.bf16:
         model = model.to(torch.bfloat16)
     model = model.to(device).eval()
+    assistant = None
+    if a.assistant_model:
+        assistant = build_model(load_config(a.assistant_model), a.assistant_model, torch_dtype="bfloat16" if a.bf16 else None)
+        if a.bf16:
+            assistant = assistant.to(torch.bfloat16)
+        assistant = assistant.to(device).eval()
     tok = load_tokenizer(a.model_name_or_path)
 
     rows = [tok.encode(p) or [getattr(tok, "bos_token_id", None) or 0] for p in prompts]
@@ -108,9 +119,13 @@ def main(argv=None):
                          temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, eos_token_id=eos,
                          pad_token_id=pad if eos is not None else None, seed=a.seed, num_beams=a.num_beams,
                          num_return_sequences=a.num_return_sequences, length_penalty=a.length_penalty,
-                         early_stopping=a.early_stopping)
+                         early_stopping=a.early_stopping, assistant_model=assistant,
+                         num_assistant_tokens=a.num_assistant_tokens, return_dict_in_generate=assistant is not None)
     sync()
     dt = time.perf_counter() - t0
+    spec = None
+    if assistant is not None:
+        spec, out = out, out.sequences
     new = out[:, width:].tolist()
     n_tokens = 0
     per = a.num_return_sequences  # rows per prompt, best beam first
@@ -122,6 +137,9 @@ def main(argv=None):
         print(f"--- {p!r}{f' [beam {j % per}]' if per > 1 else ''}\n{tok.decode(r)}")
     print(f"[generate] {len(prompts)} prompt(s), {out.shape[1] - width} steps, {n_tokens} new tokens in {dt:.3f} s: "
           f"{n_tokens / dt:.1f} tokens/s on {device}")
+    if spec is not None:
+        print(f"[generate] speculative: {spec.rounds} rounds of up to {a.num_assistant_tokens} drafts, accepted per prompt "
+              f"{spec.accepted.tolist()}")
     return out
 
 
