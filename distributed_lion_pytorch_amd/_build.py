@@ -73,7 +73,11 @@ def _flags():
 # built without SLP vectorisation: hipcc packed adjacent fp32 multiplies / FMAs
 # of the dS and exponent math into v_pk_mul_f32 / v_pk_fma_f32, which issue
 # slower than two plain ops beside MFMAs (dQ 88 -> 86 us at the GPT-2 shape)
-EXTRA_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"]}
+EXTRA_FLAGS = {
+    "attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],
+    # no packed fp32 arithmetic (v_pk_mul_f32 and kin) in the fp8-cache kernels: plain VALU ops only
+    "kv8_attention.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+}
 
 
 def _sources():

@@ -1587,6 +1587,186 @@ Tensor chunk_attention(const Tensor& q, const Tensor& k_cache, const Tensor& v_c
             "chunk_attention");
   return out;
 }
+// ---- generation on an fp8 KV cache (csrc/kv8_attention.hip, the fp8 appends of decode.hip / chunk_attention.hip)
+// codes [B, Tmax, Hkv, D] uint8, token-major with contiguous heads and 16-byte aligned token / batch strides;
+// scales [B, Tmax, Hkv] fp32 with contiguous heads
+void check_cache8(const char* what, const char* name, const Tensor& c, const Tensor& sc, int64_t B, int64_t Hkv, int64_t D) {
+  TORCH_CHECK(c.is_cuda() && c.dim() == 4 && c.scalar_type() == at::kByte && c.size(0) == B && c.size(1) >= 1 &&
+                  c.size(2) == Hkv && c.size(3) == D && c.stride(3) == 1 && (Hkv == 1 || c.stride(2) == D) &&
+                  (c.size(1) == 1 || (c.stride(1) % 16 == 0 && c.stride(1) >= Hkv * D)) &&
+                  (B == 1 || (c.stride(0) % 16 == 0 && c.stride(0) >= c.size(1) * (c.size(1) == 1 ? Hkv * D : c.stride(1)))) &&
+                  reinterpret_cast<uintptr_t>(c.data_ptr()) % 16 == 0 && c.size(1) < (int64_t{1} << 31),
+              "dlion ", what, ": ", name, " codes must be a token-major uint8 cache [B, Tmax, Hkv, D] with contiguous heads");
+  TORCH_CHECK(sc.is_cuda() && sc.dim() == 3 && sc.scalar_type() == at::kFloat && sc.size(0) == B &&
+                  sc.size(1) == c.size(1) && sc.size(2) == Hkv && (Hkv == 1 || sc.stride(2) == 1) &&
+                  (sc.size(1) == 1 || sc.stride(1) >= Hkv) && (B == 1 || sc.stride(0) >= sc.size(1) * (sc.size(1) == 1 ? Hkv : sc.stride(1))),
+              "dlion ", what, ": ", name, " scales must be fp32 [B, Tmax, Hkv] with contiguous heads");
+}
+int64_t scale_token_stride(const Tensor& s) { return s.size(1) == 1 ? s.size(2) : s.stride(1); }
+int64_t scale_batch_stride(const Tensor& s) { return s.size(0) == 1 ? s.size(1) * scale_token_stride(s) : s.stride(0); }
+
+// x [B, T, Hkv, D] bf16 -> codes[:, :T], scales[:, :T]
+void kv_quantize(const Tensor& x, const Tensor& codes, const Tensor& scales) {
+  TORCH_CHECK(x.dim() == 4, "dlion kv_quantize: x must be [B, T, Hkv, D]");
+  const int64_t B = x.size(0), T = x.size(1), Hkv = x.size(2), D = x.size(3);
+  TORCH_CHECK(D == 64 || D == 128, "dlion kv_quantize: head_dim must be 64 or 128");
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && T >= 1 && Hkv >= 1 && x.stride(3) == 1 &&
+                  (Hkv == 1 || x.stride(2) == D) && (T == 1 || (x.stride(1) % 8 == 0 && x.stride(1) >= Hkv * D)) &&
+                  (B == 1 || (x.stride(0) % 8 == 0 && x.stride(0) >= T * (T == 1 ? Hkv * D : x.stride(1)))) &&
+                  reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "dlion kv_quantize: x must be bf16 [B, T, Hkv, D] with contiguous heads and 16-byte aligned token / batch strides");
+  check_cache8("kv_quantize", "the", codes, scales, B, Hkv, D);
+  TORCH_CHECK(T <= codes.size(1), "dlion kv_quantize: ", T, " tokens do not fit a cache of ", codes.size(1));
+  const c10::DeviceGuard dg(x.device());
+  check_hip(dlion::launch_kv_quantize(x.data_ptr(), chunk_batch_stride(x), chunk_token_stride(x), codes.data_ptr<uint8_t>(),
+                                      cache_batch_stride(codes), cache_token_stride(codes), scales.data_ptr<float>(),
+                                      scale_batch_stride(scales), scale_token_stride(scales), static_cast<int>(B),
+                                      static_cast<int>(T), static_cast<int>(Hkv), static_cast<int>(D), cur_stream()),
+            "kv_quantize");
+}
+
+void check_append_tables(const char* what, const std::optional<Tensor>& cos, const std::optional<Tensor>& sin,
+                         const std::optional<Tensor>& q_gamma, const std::optional<Tensor>& k_gamma, int64_t Tmax, int64_t D) {
+  TORCH_CHECK(cos.has_value() == sin.has_value() && q_gamma.has_value() == k_gamma.has_value() &&
+                  (!q_gamma.has_value() || cos.has_value()),
+              "dlion ", what, ": cos / sin and q_gamma / k_gamma come as pairs, gains only with tables");
+  if (cos.has_value())
+    for (const Tensor* t : {&*cos, &*sin})
+      TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kBFloat16 && t->is_contiguous() && t->dim() == 2 &&
+                      t->size(0) >= Tmax && t->size(1) == D && reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                  "dlion ", what, ": cos/sin must be contiguous bf16 [>= Tmax, D]");
+  if (q_gamma.has_value())
+    for (const Tensor* g : {&*q_gamma, &*k_gamma})
+      TORCH_CHECK(g->is_cuda() && g->scalar_type() == at::kBFloat16 && g->is_contiguous() && g->numel() == D &&
+                      reinterpret_cast<uintptr_t>(g->data_ptr()) % 16 == 0,
+                  "dlion ", what, ": gains must be contiguous, 16-byte aligned bf16 [D]");
+}
+
+// kv_append on the fp8 cache: the same q_out; k and v quantised into codes / scales at cache[b, pos[b]]
+Tensor kv_append_fp8(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& pos,
+                     const std::optional<Tensor>& cos, const std::optional<Tensor>& sin,
+                     const std::optional<Tensor>& q_gamma, const std::optional<Tensor>& k_gamma, double eps,
+                     const Tensor& k_codes, const Tensor& v_codes, const Tensor& k_scales, const Tensor& v_scales,
+                     const Tensor& err) {
+  TORCH_CHECK(q.dim() == 3, "dlion kv_append_fp8: q must be [B, H, D]");
+  const int64_t B = q.size(0), H = q.size(1), D = q.size(2);
+  TORCH_CHECK(D == 64 || D == 128, "dlion kv_append_fp8: head_dim must be 64 or 128");
+  TORCH_CHECK(k.dim() == 3 && v.dim() == 3 && k.size(1) == v.size(1), "dlion kv_append_fp8: k / v must be [B, Hkv, D]");
+  const int64_t Hkv = k.size(1);
+  check_step_rows("kv_append_fp8", "q", q, B, D);
+  check_step_rows("kv_append_fp8", "k", k, B, D);
+  check_step_rows("kv_append_fp8", "v", v, B, D);
+  check_cache8("kv_append_fp8", "k", k_codes, k_scales, B, Hkv, D);
+  check_cache8("kv_append_fp8", "v", v_codes, v_scales, B, Hkv, D);
+  const int64_t Tmax = k_codes.size(1);
+  TORCH_CHECK(v_codes.size(1) == Tmax && scale_token_stride(k_scales) == scale_token_stride(v_scales) &&
+                  scale_batch_stride(k_scales) == scale_batch_stride(v_scales),
+              "dlion kv_append_fp8: the caches differ in length or their scales in strides");
+  TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == at::kInt && pos.is_contiguous() && pos.numel() == B,
+              "dlion kv_append_fp8: pos must be a contiguous int32 [B] GPU tensor");
+  TORCH_CHECK(err.is_cuda() && err.scalar_type() == at::kInt && err.numel() >= 1, "dlion kv_append_fp8: err must be int32[1]");
+  check_append_tables("kv_append_fp8", cos, sin, q_gamma, k_gamma, Tmax, D);
+  const c10::DeviceGuard dg(q.device());
+  auto q_out = at::empty({B, H, D}, q.options());
+  check_hip(dlion::launch_kv_append_fp8(
+                q.data_ptr(), k.data_ptr(), v.data_ptr(), step_row_stride(q), step_row_stride(k), step_row_stride(v),
+                pos.data_ptr<int>(), cos.has_value() ? cos->data_ptr() : nullptr,
+                sin.has_value() ? sin->data_ptr() : nullptr, q_gamma.has_value() ? q_gamma->data_ptr() : nullptr,
+                k_gamma.has_value() ? k_gamma->data_ptr() : nullptr, static_cast<float>(eps), q_out.data_ptr(),
+                k_codes.data_ptr<uint8_t>(), v_codes.data_ptr<uint8_t>(), cache_batch_stride(k_codes),
+                cache_token_stride(k_codes), cache_batch_stride(v_codes), cache_token_stride(v_codes),
+                k_scales.data_ptr<float>(), v_scales.data_ptr<float>(), scale_batch_stride(k_scales),
+                scale_token_stride(k_scales), static_cast<int>(B), static_cast<int>(H), static_cast<int>(Hkv),
+                static_cast<int>(D), static_cast<int>(Tmax), err.data_ptr<int>(), cur_stream()),
+            "kv_append_fp8");
+  return q_out;
+}
+
+Tensor kv_append_chunk_fp8(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& pos,
+                           const std::optional<Tensor>& n_new, const std::optional<Tensor>& cos,
+                           const std::optional<Tensor>& sin, const std::optional<Tensor>& q_gamma,
+                           const std::optional<Tensor>& k_gamma, double eps, const Tensor& k_codes,
+                           const Tensor& v_codes, const Tensor& k_scales, const Tensor& v_scales, const Tensor& err) {
+  TORCH_CHECK(q.dim() == 4, "dlion kv_append_chunk_fp8: q must be [B, T, H, D]");
+  const int64_t B = q.size(0), T = q.size(1), H = q.size(2), D = q.size(3);
+  TORCH_CHECK(D == 64 || D == 128, "dlion kv_append_chunk_fp8: head_dim must be 64 or 128");
+  TORCH_CHECK(T >= 1 && T <= dlion::kChunkMaxTokens, "dlion kv_append_chunk_fp8: T must be in [1, 8]");
+  TORCH_CHECK(k.dim() == 4 && v.dim() == 4 && k.size(2) == v.size(2), "dlion kv_append_chunk_fp8: k / v must be [B, T, Hkv, D]");
+  const int64_t Hkv = k.size(2);
+  check_chunk_rows("kv_append_chunk_fp8", "q", q, B, T, D);
+  check_chunk_rows("kv_append_chunk_fp8", "k", k, B, T, D);
+  check_chunk_rows("kv_append_chunk_fp8", "v", v, B, T, D);
+  check_cache8("kv_append_chunk_fp8", "k", k_codes, k_scales, B, Hkv, D);
+  check_cache8("kv_append_chunk_fp8", "v", v_codes, v_scales, B, Hkv, D);
+  const int64_t Tmax = k_codes.size(1);
+  TORCH_CHECK(v_codes.size(1) == Tmax && scale_token_stride(k_scales) == scale_token_stride(v_scales) &&
+                  scale_batch_stride(k_scales) == scale_batch_stride(v_scales),
+              "dlion kv_append_chunk_fp8: the caches differ in length or their scales in strides");
+  TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == at::kInt && pos.is_contiguous() && pos.numel() == B,
+              "dlion kv_append_chunk_fp8: pos must be a contiguous int32 [B] GPU tensor");
+  const int* nn = chunk_n_new("kv_append_chunk_fp8", n_new, B);
+  TORCH_CHECK(err.is_cuda() && err.scalar_type() == at::kInt && err.numel() >= 1,
+              "dlion kv_append_chunk_fp8: err must be int32[1]");
+  check_append_tables("kv_append_chunk_fp8", cos, sin, q_gamma, k_gamma, Tmax, D);
+  const c10::DeviceGuard dg(q.device());
+  auto q_out = at::empty({B, T, H, D}, q.options());
+  check_hip(dlion::launch_kv_append_chunk_fp8(
+                q.data_ptr(), k.data_ptr(), v.data_ptr(), chunk_batch_stride(q), chunk_token_stride(q),
+                chunk_batch_stride(k), chunk_token_stride(k), chunk_batch_stride(v), chunk_token_stride(v),
+                pos.data_ptr<int>(), nn, cos.has_value() ? cos->data_ptr() : nullptr,
+                sin.has_value() ? sin->data_ptr() : nullptr, q_gamma.has_value() ? q_gamma->data_ptr() : nullptr,
+                k_gamma.has_value() ? k_gamma->data_ptr() : nullptr, static_cast<float>(eps), q_out.data_ptr(),
+                k_codes.data_ptr<uint8_t>(), v_codes.data_ptr<uint8_t>(), cache_batch_stride(k_codes),
+                cache_token_stride(k_codes), cache_batch_stride(v_codes), cache_token_stride(v_codes),
+                k_scales.data_ptr<float>(), v_scales.data_ptr<float>(), scale_batch_stride(k_scales),
+                scale_token_stride(k_scales), static_cast<int>(B), static_cast<int>(T), static_cast<int>(H),
+                static_cast<int>(Hkv), static_cast<int>(D), static_cast<int>(Tmax), err.data_ptr<int>(), cur_stream()),
+            "kv_append_chunk_fp8");
+  return q_out;
+}
+
+// out [B, T, H D]; splits / chunk from ops/fused.py chunk_splits
+Tensor cached_attention_fp8(const Tensor& q, const Tensor& k_codes, const Tensor& k_scales, const Tensor& v_codes,
+                            const Tensor& v_scales, const Tensor& kv_len, const std::optional<Tensor>& n_new,
+                            int64_t window, int64_t max_len, int64_t splits, int64_t chunk) {
+  TORCH_CHECK(q.dim() == 4 && k_codes.dim() == 4,
+              "dlion cached_attention_fp8: q must be [B, T, H, D], the codes [B, Tmax, Hkv, D]");
+  const int64_t B = q.size(0), T = q.size(1), H = q.size(2), D = q.size(3), Tmax = k_codes.size(1), Hkv = k_codes.size(2);
+  TORCH_CHECK(D == 64 || D == 128, "dlion cached_attention_fp8: head_dim must be 64 or 128");
+  TORCH_CHECK(T >= 1 && T <= dlion::kChunkMaxTokens, "dlion cached_attention_fp8: T must be in [1, 8]");
+  TORCH_CHECK(Hkv >= 1 && H % Hkv == 0 && H / Hkv <= 8, "dlion cached_attention_fp8: H / Hkv must be an integer in [1, 8]");
+  TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16 && q.is_contiguous() &&
+                  reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0,
+              "dlion cached_attention_fp8: q must be a contiguous, 16-byte aligned bf16 GPU tensor");
+  check_cache8("cached_attention_fp8", "k", k_codes, k_scales, B, Hkv, D);
+  check_cache8("cached_attention_fp8", "v", v_codes, v_scales, B, Hkv, D);
+  TORCH_CHECK(v_codes.size(1) == Tmax, "dlion cached_attention_fp8: the caches differ in length");
+  TORCH_CHECK(kv_len.is_cuda() && kv_len.scalar_type() == at::kInt && kv_len.is_contiguous() && kv_len.numel() == B,
+              "dlion cached_attention_fp8: kv_len must be a contiguous int32 [B] GPU tensor");
+  const int* nn = chunk_n_new("cached_attention_fp8", n_new, B);
+  TORCH_CHECK(max_len >= 1 && max_len < (int64_t{1} << 31) && window >= 0 && window < (int64_t{1} << 30) &&
+                  splits >= 1 && splits <= dlion::kDecodeMaxSplits && chunk >= 1 && chunk < (int64_t{1} << 31) &&
+                  B <= 65535 && Hkv <= 65535,
+              "dlion cached_attention_fp8: bad max_len / window / splits / chunk / batch");
+  const c10::DeviceGuard dg(q.device());
+  const auto f32 = q.options().dtype(at::kFloat);
+  auto part_ml = at::empty({2, B, T, H, splits}, f32);
+  auto part_o = at::empty({B, T, H, splits, D}, f32);
+  auto out = at::empty({B, T, H * D}, q.options());
+  float* pm = part_ml.data_ptr<float>();
+  check_hip(dlion::launch_cached_attention_fp8(
+                q.data_ptr(), k_codes.data_ptr<uint8_t>(), cache_batch_stride(k_codes), cache_token_stride(k_codes),
+                k_scales.data_ptr<float>(), scale_batch_stride(k_scales), scale_token_stride(k_scales),
+                v_codes.data_ptr<uint8_t>(), cache_batch_stride(v_codes), cache_token_stride(v_codes),
+                v_scales.data_ptr<float>(), scale_batch_stride(v_scales), scale_token_stride(v_scales),
+                kv_len.data_ptr<int>(), nn, pm, pm + B * T * H * splits, part_o.data_ptr<float>(), out.data_ptr(),
+                static_cast<int>(B), static_cast<int>(T), static_cast<int>(H), static_cast<int>(Hkv),
+                static_cast<int>(D), static_cast<int>(Tmax), static_cast<int>(max_len), static_cast<int>(window),
+                static_cast<int>(splits), static_cast<int>(chunk), 1.0f / std::sqrt(static_cast<float>(D)), cur_stream()),
+            "cached_attention_fp8");
+  return out;
+}
+
 // ---- decode projections (csrc/skinny_gemm.hip)
 // the operands both forms share: x [M, K] bf16 rows (unit inner stride, 16-byte aligned base and row stride), out a
 // row-major bf16 [M, N] view with its own leading dimension, bias contiguous bf16 [N]; (splits, per) from
@@ -1673,6 +1853,15 @@ TORCH_LIBRARY(dlion, m) {
         " Tensor? q_gamma, Tensor? k_gamma, float eps, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor(c!) err) -> Tensor");
   m.def("chunk_attention(Tensor q, Tensor k_cache, Tensor v_cache, Tensor kv_len, Tensor? n_new, int window,"
         " int max_len, int splits, int chunk) -> Tensor");
+  m.def("kv_quantize(Tensor x, Tensor(a!) codes, Tensor(b!) scales) -> ()");
+  m.def("kv_append_fp8(Tensor q, Tensor k, Tensor v, Tensor pos, Tensor? cos, Tensor? sin, Tensor? q_gamma,"
+        " Tensor? k_gamma, float eps, Tensor(a!) k_codes, Tensor(b!) v_codes, Tensor(c!) k_scales, Tensor(d!) v_scales,"
+        " Tensor(e!) err) -> Tensor");
+  m.def("kv_append_chunk_fp8(Tensor q, Tensor k, Tensor v, Tensor pos, Tensor? n_new, Tensor? cos, Tensor? sin,"
+        " Tensor? q_gamma, Tensor? k_gamma, float eps, Tensor(a!) k_codes, Tensor(b!) v_codes, Tensor(c!) k_scales,"
+        " Tensor(d!) v_scales, Tensor(e!) err) -> Tensor");
+  m.def("cached_attention_fp8(Tensor q, Tensor k_codes, Tensor k_scales, Tensor v_codes, Tensor v_scales, Tensor kv_len,"
+        " Tensor? n_new, int window, int max_len, int splits, int chunk) -> Tensor");
   m.def("quant4(Tensor w, Tensor code) -> (Tensor, Tensor)");
   m.def("dequant4_(Tensor q, Tensor absmax, Tensor code, Tensor(a!) out) -> ()");
   m.def("gemm_tn(Tensor[] P, Tensor[] Q, int splits) -> Tensor");
@@ -1813,6 +2002,10 @@ TORCH_LIBRARY_IMPL(dlion, CUDA, m) {
   m.impl("decode_attention", &decode_attention);
   m.impl("kv_append_chunk", &kv_append_chunk);
   m.impl("chunk_attention", &chunk_attention);
+  m.impl("kv_quantize", &kv_quantize);
+  m.impl("kv_append_fp8", &kv_append_fp8);
+  m.impl("kv_append_chunk_fp8", &kv_append_chunk_fp8);
+  m.impl("cached_attention_fp8", &cached_attention_fp8);
   m.impl("skinny_gemm_nt", &skinny_gemm_nt);
   m.impl("skinny_gemm_w4", &skinny_gemm_w4);
 }

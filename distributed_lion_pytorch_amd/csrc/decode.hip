@@ -23,111 +23,15 @@
 // Nothing at or beyond kv_len[b] is read: key indices are clamped into the block's own non-empty range
 // before an address is formed and the clamped lanes' scores are -inf.  A block whose range is empty loads
 // nothing and writes the neutral partial (max -inf, sum 0, output 0).
+//
+// The kv_append kernel itself is in kv_append.h, shared with the fp8 cache's stores (kv8_attention.hip).
 #include "common.h"
 #include "kernels.h"
+#include "kv_append.h"
 #include "rope_norm.h"
 
 namespace dlion {
 namespace {
-
-using E = Elem<kBF16>;
-
-__device__ __forceinline__ void unpack8(const uint4& r, float (&o)[8]) {
-  const uint32_t w[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    o[2 * i] = bf16_to_f32(static_cast<uint16_t>(w[i] & 0xffffu));
-    o[2 * i + 1] = bf16_to_f32(static_cast<uint16_t>(w[i] >> 16));
-  }
-}
-__device__ __forceinline__ void unpack4(const uint2& r, float (&o)[4]) {
-  o[0] = bf16_to_f32(static_cast<uint16_t>(r.x & 0xffffu));
-  o[1] = bf16_to_f32(static_cast<uint16_t>(r.x >> 16));
-  o[2] = bf16_to_f32(static_cast<uint16_t>(r.y & 0xffffu));
-  o[3] = bf16_to_f32(static_cast<uint16_t>(r.y >> 16));
-}
-__device__ __forceinline__ uint2 pack4(const float (&o)[4]) {
-  uint2 v;
-  v.x = static_cast<uint32_t>(f32_to_bf16(o[0])) | (static_cast<uint32_t>(f32_to_bf16(o[1])) << 16);
-  v.y = static_cast<uint32_t>(f32_to_bf16(o[2])) | (static_cast<uint32_t>(f32_to_bf16(o[3])) << 16);
-  return v;
-}
-
-enum : int { kAppend = 0, kRope = 1, kNormRope = 2 };
-
-// grid: ceil(B (H + 2 Hkv) / GROUPS) blocks of 256; a lane group of D / 8 lanes owns one head row of one
-// sequence: slots [0, H) are q, [H, H + Hkv) k, the rest v
-template <int D, int MODE>
-__global__ void __launch_bounds__(256) kv_append_kernel(
-    const uint16_t* __restrict__ q, const uint16_t* __restrict__ k, const uint16_t* __restrict__ v, int64_t q_ld,
-    int64_t k_ld, int64_t v_ld, const int* __restrict__ pos, const uint16_t* __restrict__ cs,
-    const uint16_t* __restrict__ sn, const uint16_t* __restrict__ gq, const uint16_t* __restrict__ gk, float eps,
-    uint16_t* __restrict__ q_out, uint16_t* __restrict__ kc, uint16_t* __restrict__ vc, int64_t kc_bs, int64_t kc_ts,
-    int64_t vc_bs, int64_t vc_ts, int B, int H, int Hkv, int Tmax, int32_t* __restrict__ err) {
-  constexpr int LANES = D / 8, GROUPS = 256 / LANES;
-  const int sub = threadIdx.x % LANES, grp = threadIdx.x / LANES;
-  const int Hx = H + 2 * Hkv;
-  const int64_t n_hr = static_cast<int64_t>(B) * Hx;
-  const int64_t hr = static_cast<int64_t>(blockIdx.x) * GROUPS + grp;
-  const bool valid = hr < n_hr;
-  const int64_t hrc = valid ? hr : n_hr - 1;
-  const int b = static_cast<int>(hrc / Hx);
-  const int slot = static_cast<int>(hrc - static_cast<int64_t>(b) * Hx);
-  int p = pos[b];
-  if (p < 0 || p >= Tmax) {  // an error (flag checked once per step, ops/fused.py), never a write outside the cache
-    if (valid && sub == 0 && slot == 0) atomicOr(err, kIndexErrCache);
-    p = p < 0 ? 0 : Tmax - 1;
-  }
-  const bool is_q = slot < H, is_v = slot >= H + Hkv;
-  const uint16_t* src = is_q    ? q + b * q_ld + static_cast<int64_t>(slot) * D
-                        : is_v  ? v + b * v_ld + static_cast<int64_t>(slot - H - Hkv) * D
-                                : k + b * k_ld + static_cast<int64_t>(slot - H) * D;
-  uint16_t* dst = is_q   ? q_out + (static_cast<int64_t>(b) * H + slot) * D
-                  : is_v ? vc + b * vc_bs + p * vc_ts + static_cast<int64_t>(slot - H - Hkv) * D
-                         : kc + b * kc_bs + p * kc_ts + static_cast<int64_t>(slot - H) * D;
-  if constexpr (MODE == kRope) {
-    // rope_kernel's mapping: 4 dims of the first half and their partners in the second
-    constexpr int hd = D / 2;
-    const int d0 = sub * 4;
-    const uint2 ra = *reinterpret_cast<const uint2*>(src + d0);
-    const uint2 rb = *reinterpret_cast<const uint2*>(src + hd + d0);
-    const int64_t tb = static_cast<int64_t>(p) * D + d0;
-    float a[4], bb[4], ca[4], cb[4], sa[4], sb[4], oa[4], ob[4];
-    unpack4(ra, a);
-    unpack4(rb, bb);
-    unpack4(*reinterpret_cast<const uint2*>(cs + tb), ca);
-    unpack4(*reinterpret_cast<const uint2*>(cs + tb + hd), cb);
-    unpack4(*reinterpret_cast<const uint2*>(sn + tb), sa);
-    unpack4(*reinterpret_cast<const uint2*>(sn + tb + hd), sb);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) rope_forward(a[j], bb[j], ca[j], cb[j], sa[j], sb[j], oa[j], ob[j]);
-    if (valid) {
-      *reinterpret_cast<uint2*>(dst + d0) = is_v ? ra : pack4(oa);
-      *reinterpret_cast<uint2*>(dst + hd + d0) = is_v ? rb : pack4(ob);
-    }
-  } else {
-    const int d0 = sub * 8;
-    const uint4 raw = *reinterpret_cast<const uint4*>(src + d0);
-    if constexpr (MODE == kAppend) {
-      if (valid) *reinterpret_cast<uint4*>(dst + d0) = raw;
-    } else {
-      // qk_norm.hip's mapping; v rows run the same lanes (their result is dropped) so that no DPP move
-      // reads an inactive lane
-      float x[8], w[8], c[8], s[8], o[8];
-      unpack8(raw, x);
-      E::load8((is_q ? gq : gk) + d0, w);
-      E::load8(cs + static_cast<int64_t>(p) * D + d0, c);
-      E::load8(sn + static_cast<int64_t>(p) * D + d0, s);
-      qk_norm_rope_row<LANES>(x, w, c, s, eps, sub < LANES / 2, o);
-      if (valid) {
-        if (is_v)
-          *reinterpret_cast<uint4*>(dst + d0) = raw;
-        else
-          E::store8(dst + d0, o);
-      }
-    }
-  }
-}
 
 // ------------------------------------------------------------------------------------ decode attention
 constexpr float kNegInf = -__builtin_huge_valf();
@@ -302,38 +206,8 @@ hipError_t launch_kv_append(const void* q, const void* k, const void* v, int64_t
                             const void* k_gamma, float eps, void* q_out, void* k_cache, void* v_cache, int64_t kc_bs,
                             int64_t kc_ts, int64_t vc_bs, int64_t vc_ts, int B, int H, int Hkv, int D, int Tmax,
                             int32_t* err, hipStream_t st) {
-  if (B <= 0 || H <= 0 || Hkv <= 0) return hipSuccess;
-  if ((D != 64 && D != 128) || Tmax <= 0 || err == nullptr) return hipErrorInvalidValue;
-  if ((cos == nullptr) != (sin == nullptr) || (q_gamma == nullptr) != (k_gamma == nullptr)) return hipErrorInvalidValue;
-  if (q_gamma != nullptr && cos == nullptr) return hipErrorInvalidValue;
-  const int groups = 256 / (D / 8);
-  const int64_t n_hr = static_cast<int64_t>(B) * (H + 2 * Hkv);
-  const dim3 grid(static_cast<unsigned>((n_hr + groups - 1) / groups));
-  auto* Q = static_cast<const uint16_t*>(q);
-  auto* K = static_cast<const uint16_t*>(k);
-  auto* V = static_cast<const uint16_t*>(v);
-  auto* C = static_cast<const uint16_t*>(cos);
-  auto* S = static_cast<const uint16_t*>(sin);
-  auto* GQ = static_cast<const uint16_t*>(q_gamma);
-  auto* GK = static_cast<const uint16_t*>(k_gamma);
-  auto* QO = static_cast<uint16_t*>(q_out);
-  auto* KC = static_cast<uint16_t*>(k_cache);
-  auto* VC = static_cast<uint16_t*>(v_cache);
-#define DLION_KV_APPEND(DD, MODE)                                                                                    \
-  hipLaunchKernelGGL((kv_append_kernel<DD, MODE>), grid, dim3(256), 0, st, Q, K, V, q_ld, k_ld, v_ld, pos, C, S, GQ, \
-                     GK, eps, QO, KC, VC, kc_bs, kc_ts, vc_bs, vc_ts, B, H, Hkv, Tmax, err)
-  const int mode = q_gamma != nullptr ? kNormRope : (cos != nullptr ? kRope : kAppend);
-  if (D == 128) {
-    if (mode == kNormRope) DLION_KV_APPEND(128, kNormRope);
-    else if (mode == kRope) DLION_KV_APPEND(128, kRope);
-    else DLION_KV_APPEND(128, kAppend);
-  } else {
-    if (mode == kNormRope) DLION_KV_APPEND(64, kNormRope);
-    else if (mode == kRope) DLION_KV_APPEND(64, kRope);
-    else DLION_KV_APPEND(64, kAppend);
-  }
-#undef DLION_KV_APPEND
-  return hipGetLastError();
+  return kv_append_any<false>(q, k, v, q_ld, k_ld, v_ld, pos, cos, sin, q_gamma, k_gamma, eps, q_out, k_cache, v_cache,
+                              kc_bs, kc_ts, vc_bs, vc_ts, nullptr, nullptr, 0, 0, B, H, Hkv, D, Tmax, err, st);
 }
 
 hipError_t launch_decode_attention(const void* q, int64_t q_ld, const void* k_cache, int64_t k_bs, int64_t k_ts,

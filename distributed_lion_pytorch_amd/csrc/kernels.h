@@ -224,6 +224,35 @@ hipError_t launch_chunk_attention(const void* q, const void* k_cache, int64_t k_
                                   int T, int H, int Hkv, int D, int Tmax, int max_len, int window, int splits,
                                   int chunk, float scale, hipStream_t st);
 
+// ---- generation on an fp8 KV cache (kv8.h, kv8_attention.hip; the appends in decode.hip / chunk_attention.hip)
+// The cache: codes uint8 [B, Tmax, Hkv, D] (OCP e4m3fn; batch / token strides in bytes, heads contiguous, 16-byte
+// aligned) and scales fp32 [B, Tmax, Hkv] (batch / token strides in elements), one power of two per (token, kv head).
+// x bf16 [B, T, Hkv, D] (strides x_bs / x_ts, heads contiguous) -> codes[b, t], scales[b, t] for every t < T
+hipError_t launch_kv_quantize(const void* x, int64_t x_bs, int64_t x_ts, uint8_t* codes, int64_t c_bs, int64_t c_ts,
+                              float* scales, int64_t s_bs, int64_t s_ts, int B, int T, int Hkv, int D, hipStream_t st);
+// launch_kv_append / launch_kv_append_chunk with the quantiser in their k / v stores: the same positions, error
+// flag and q_out bits; k_scales and v_scales share their strides sc_bs / sc_ts
+hipError_t launch_kv_append_fp8(const void* q, const void* k, const void* v, int64_t q_ld, int64_t k_ld, int64_t v_ld,
+                                const int* pos, const void* cos, const void* sin, const void* q_gamma,
+                                const void* k_gamma, float eps, void* q_out, uint8_t* k_codes, uint8_t* v_codes,
+                                int64_t kc_bs, int64_t kc_ts, int64_t vc_bs, int64_t vc_ts, float* k_scales,
+                                float* v_scales, int64_t sc_bs, int64_t sc_ts, int B, int H, int Hkv, int D, int Tmax,
+                                int32_t* err, hipStream_t st);
+hipError_t launch_kv_append_chunk_fp8(const void* q, const void* k, const void* v, int64_t q_bs, int64_t q_ts,
+                                      int64_t k_bs, int64_t k_ts, int64_t v_bs, int64_t v_ts, const int* pos,
+                                      const int* n_new, const void* cos, const void* sin, const void* q_gamma,
+                                      const void* k_gamma, float eps, void* q_out, uint8_t* k_codes, uint8_t* v_codes,
+                                      int64_t kc_bs, int64_t kc_ts, int64_t vc_bs, int64_t vc_ts, float* k_scales,
+                                      float* v_scales, int64_t sc_bs, int64_t sc_ts, int B, int T, int H, int Hkv,
+                                      int D, int Tmax, int32_t* err, hipStream_t st);
+// launch_chunk_attention on the fp8 cache (the same key ranges, grid and partials); T = 1 is the decode step
+hipError_t launch_cached_attention_fp8(const void* q, const uint8_t* k_codes, int64_t k_bs, int64_t k_ts,
+                                       const float* k_scales, int64_t ks_bs, int64_t ks_ts, const uint8_t* v_codes,
+                                       int64_t v_bs, int64_t v_ts, const float* v_scales, int64_t vs_bs, int64_t vs_ts,
+                                       const int* kv_len, const int* n_new, float* part_m, float* part_l,
+                                       float* part_o, void* out, int B, int T, int H, int Hkv, int D, int Tmax,
+                                       int max_len, int window, int splits, int chunk, float scale, hipStream_t st);
+
 // ---- decode projections (skinny_gemm.hip); bf16, 1 <= M <= 16, K % 64 == 0, any N
 // out[M, N] (row stride ldo) = x[M, K] (row stride ldx, 16-byte aligned rows) . w[N, K]^T (+ bias[N]), fp32
 // accumulation, one rounding.  The 128-k steps of K are cut into `splits` runs of `per` steps ((splits - 1) per <

@@ -8,6 +8,13 @@ prompt through the flash forward), every later call one decode step (one token p
 by ``n_new`` (``fused.kv_append_chunk`` and ``fused.chunk_attention``, csrc/chunk_attention.hip);
 ``KVCache.truncate`` rolls rows back.
 
+``KVCache(..., kv_dtype="fp8_e4m3")`` (``generate(kv_cache_dtype="fp8_e4m3")``) holds e4m3 codes and one power-of-two
+fp32 scale per (token, kv head) instead: (D + 4) / 2D of the bf16 cache's memory.  The prefill quantises the rotated
+k and v with ``fused.kv_quantize`` (the prompt's own attention stays the flash forward on the unquantised k and v),
+a step or a chunk appends through the fp8 stores of ``fused.kv_append`` / ``kv_append_chunk`` and attends through
+``fused.cached_attention_fp8`` (csrc/kv8_attention.hip).  Only the cached keys and values are quantised; the tokens
+may differ from the bf16 cache's.
+
 ``NativeGenerateMixin.generate`` uses HF's argument names: greedy or sampled (temperature, then top-k, then
 top-p), ragged prompts by ``attention_mask`` (left- or right-padded), EOS / pad handling; ``num_beams > 1`` is beam
 search (HF's semantics) on ``fused.lm_head_topk``; ``assistant_model`` is greedy speculative decoding (a draft
@@ -25,6 +32,7 @@ from ..ops import fused
 from ..ops.linear import gemm_fwd
 
 _EOS_CHECK_EVERY = 8  # decode steps between two host reads of "every row has finished"
+KV_CACHE_DTYPES = (None, "fp8_e4m3")  # None: the model's dtype
 
 
 class GenerateOutput(NamedTuple):
@@ -58,13 +66,19 @@ class KVCache:
     Allocated once per ``generate`` call.  ``width`` is the host's bound on the lengths (prompt width plus
     steps taken): it sizes the decode grid and refuses a step past ``max_len`` without a device sync."""
 
-    def __init__(self, config, batch: int, max_len: int, device=None, dtype=torch.float32):
+    def __init__(self, config, batch: int, max_len: int, device=None, dtype=torch.float32, kv_dtype=None):
         layers, hkv, hd = cache_geometry(config)
         self.batch, self.max_len = int(batch), int(max_len)
         if self.batch < 1 or self.max_len < 1:
             raise ValueError("KVCache: batch and max_len must be positive")
-        # one allocation: [layer, k | v, B, max_len, Hkv, D]
-        self._buf = torch.zeros(layers, 2, self.batch, self.max_len, hkv, hd, device=device, dtype=dtype)
+        if kv_dtype not in KV_CACHE_DTYPES:
+            raise ValueError(f"KVCache: kv_dtype must be one of {KV_CACHE_DTYPES}, got {kv_dtype!r}")
+        self.kv_dtype = kv_dtype
+        # one allocation: [layer, k | v, B, max_len, Hkv, D]; "fp8_e4m3": e4m3 codes (uint8) and one fp32 scale per
+        # (token, kv head) in a second one (ops/fused.py kv_quantize_reference has the format)
+        self._buf = torch.zeros(layers, 2, self.batch, self.max_len, hkv, hd, device=device,
+                                dtype=dtype if kv_dtype is None else torch.uint8)
+        self._scales = None if kv_dtype is None else torch.zeros(layers, 2, self.batch, self.max_len, hkv, device=device)
         self.lengths = torch.zeros(self.batch, dtype=torch.int32, device=device)
         self.kv_len = self.lengths  # lengths + 1 during a decode step
         self.width = 0
@@ -73,8 +87,14 @@ class KVCache:
         self.n_new = None  # int32 [B]: the tokens of the chunk in flight that row b keeps (None: all T)
 
     def layer(self, i: int):
-        """(k, v) of layer i, each [B, max_len, Hkv, D]."""
+        """(k, v) of layer i, each [B, max_len, Hkv, D] (an fp8 cache: the codes)."""
         return self._buf[i, 0], self._buf[i, 1]
+
+    def layer_scales(self, i: int):
+        """(k scales, v scales) of layer i of an fp8 cache, each fp32 [B, max_len, Hkv]; (None, None) otherwise."""
+        if self._scales is None:
+            return None, None
+        return self._scales[i, 0], self._scales[i, 1]
 
     def begin(self, B: int, T: int, n_new: Optional[torch.Tensor] = None) -> bool:
         """Start a forward of T tokens per row; True for the prefill (the first call).  After the prefill T = 1
@@ -141,12 +161,19 @@ class KVCache:
         if n < 1:
             raise ValueError("KVCache.repeat_rows: n must be >= 1")
         out = object.__new__(KVCache)
-        out.batch, out.max_len = self.batch * n, self.max_len
-        shape = list(self._buf.shape)
-        shape[2] = out.batch
-        out._buf = torch.zeros(shape, device=self._buf.device, dtype=self._buf.dtype)
+        out.batch, out.max_len, out.kv_dtype = self.batch * n, self.max_len, self.kv_dtype
         w = self.width
-        out._buf[:, :, :, :w] = self._buf[:, :, :, :w].repeat_interleave(n, dim=2)
+
+        def repeated(buf):
+            if buf is None:
+                return None
+            shape = list(buf.shape)
+            shape[2] = out.batch
+            new = torch.zeros(shape, device=buf.device, dtype=buf.dtype)
+            new[:, :, :, :w] = buf[:, :, :, :w].repeat_interleave(n, dim=2)
+            return new
+
+        out._buf, out._scales = repeated(self._buf), repeated(self._scales)
         out.lengths = self.lengths.repeat_interleave(n)
         out.kv_len = out.lengths
         out.width, out.prefilled = self.width, self.prefilled
@@ -159,8 +186,8 @@ class KVCache:
         same keys (a shared prompt), so the move costs the generated suffix, not the context."""
         lo = max(0, int(lo))
         if lo < self.width:
-            part = self._buf[:, :, :, lo:self.width]
-            self._buf[:, :, :, lo:self.width] = part.index_select(2, index)
+            for buf in (self._buf,) if self._scales is None else (self._buf, self._scales):
+                buf[:, :, :, lo:self.width] = buf[:, :, :, lo:self.width].index_select(2, index)
         self.lengths.copy_(self.lengths.index_select(0, index))
 
 
@@ -219,7 +246,7 @@ class NativeGenerateMixin:
                  top_p: float = 1.0, eos_token_id=None, pad_token_id: Optional[int] = None,
                  seed: Optional[int] = None, num_beams: int = 1, num_return_sequences: int = 1,
                  length_penalty: float = 1.0, early_stopping: bool = False, return_dict_in_generate: bool = False,
-                 assistant_model=None, num_assistant_tokens: int = 5):
+                 assistant_model=None, num_assistant_tokens: int = 5, kv_cache_dtype: Optional[str] = None):
         """[B, T0] prompts -> [B, T0 + n_new] long: the prompt exactly as given, then the new tokens.
 
         Greedy takes the top-1 of ``fused.lm_head_score`` (the lowest id on ties, no [B, V] tensor); sampling
@@ -240,7 +267,17 @@ class NativeGenerateMixin:
         single-token steps and this model checks them in one chunk forward (``fused.chunk_attention``), keeping
         the longest prefix it agrees with plus its own next token -- the tokens plain greedy decoding produces,
         for fewer passes over this model's weights.  ``return_dict_in_generate=True`` then returns
-        :class:`SpeculativeOutput`."""
+        :class:`SpeculativeOutput`.
+
+        ``kv_cache_dtype="fp8_e4m3"`` keeps the cached keys and values as e4m3 codes with one power-of-two fp32 scale
+        per (token, kv head) (``fused.kv_quantize``, the fp8 stores of ``fused.kv_append`` / ``kv_append_chunk``,
+        ``fused.cached_attention_fp8``): the cache takes (D + 4) / 2D of the bf16 cache's memory (0.52 at head_dim
+        128, 0.53 at 64).  Only what is cached is quantised -- the prompt's own attention in the prefill runs on the
+        unquantised k and v, q and the probabilities stay bf16 / fp32 -- so the tokens may differ from the bf16
+        cache's wherever two logits are closer than the quantisation error.  With ``assistant_model`` this model's
+        cache takes the type and the assistant's stays in its own dtype.  Default None: the model's dtype."""
+        if kv_cache_dtype not in KV_CACHE_DTYPES:
+            raise ValueError(f"generate: kv_cache_dtype must be one of {KV_CACHE_DTYPES}, got {kv_cache_dtype!r}")
         num_beams, num_return_sequences = int(num_beams), int(num_return_sequences)
         if num_beams < 1:
             raise ValueError("generate: num_beams must be >= 1")
@@ -295,16 +332,17 @@ class NativeGenerateMixin:
         ids, lens = left_align(input_ids, attention_mask)
         weight = self.lm_head.weight
         if assistant_model is not None:
-            out = self._speculative(assistant_model, input_ids, ids, lens, max_new_tokens, eos, pad_token_id, k)
+            out = self._speculative(assistant_model, input_ids, ids, lens, max_new_tokens, eos, pad_token_id, k,
+                                    kv_cache_dtype)
             fused.check_index_errors()
             return out if return_dict_in_generate else out.sequences
         if num_beams > 1:
             lo = T0 if attention_mask is None else int(lens.min())
             out = self._beam_search(input_ids, ids, lens, lo, max_new_tokens, eos, pad_token_id, num_beams,
-                                    num_return_sequences, float(length_penalty), early_stopping)
+                                    num_return_sequences, float(length_penalty), early_stopping, kv_cache_dtype)
             fused.check_index_errors()
             return out if return_dict_in_generate else out.sequences
-        cache = KVCache(cfg, B, total, dev, weight.dtype)
+        cache = KVCache(cfg, B, total, dev, weight.dtype, kv_cache_dtype)
         gen = None
         if do_sample and seed is not None:
             gen = torch.Generator(device=dev)
@@ -344,7 +382,7 @@ class NativeGenerateMixin:
         out = torch.cat([input_ids, new[:, :n_new]], dim=1)
         return GenerateOutput(out, None) if return_dict_in_generate else out
 
-    def _speculative(self, assistant, input_ids, ids, lens, n, eos, pad_token_id, k):
+    def _speculative(self, assistant, input_ids, ids, lens, n, eos, pad_token_id, k, kv_cache_dtype=None):
         """Greedy speculative decoding.  Row b has emitted ``count[b]`` tokens, the last of which (``last``) is not
         in the target's cache yet; the assistant's cache lacks the last one or two of them (``unseen``: two when
         every draft of the previous round was accepted, since the last draft was never fed to the assistant).  A
@@ -361,7 +399,7 @@ class NativeGenerateMixin:
         limit_t = min(size, cfg.n_positions) if cfg.model_type == "gpt2" else size
         limit_a = min(size, acfg.n_positions) if acfg.model_type == "gpt2" else size
         rows = torch.arange(B, device=dev)
-        cache = KVCache(cfg, B, size, dev, weight.dtype)
+        cache = KVCache(cfg, B, size, dev, weight.dtype, kv_cache_dtype)
         a_cache = KVCache(acfg, B, size, dev, a_weight.dtype)
         h = base(ids, cache=cache)[rows, lens - 1]
         cache.set_lengths(lens)
@@ -436,7 +474,8 @@ class NativeGenerateMixin:
         out = torch.cat([input_ids, new[:, :n_out]], dim=1)
         return SpeculativeOutput(out, None, rounds, accepted)
 
-    def _beam_search(self, input_ids, ids, lens, lo, n, eos, pad_token_id, nb, n_ret, length_penalty, early_stopping):
+    def _beam_search(self, input_ids, ids, lens, lo, n, eos, pad_token_id, nb, n_ret, length_penalty, early_stopping,
+                     kv_cache_dtype=None):
         """transformers' ``GenerationMixin._beam_search`` on the native cache: the same running / finished beam
         sets, scores and stopping rules, with two differences in mechanics.  The candidates of a step are the
         ``keep`` best continuations of every beam (``fused.lm_head_topk``: values - logsumexp are the
@@ -453,7 +492,7 @@ class NativeGenerateMixin:
                              f"{min(fused.LM_TOPK_MAX, cfg.vocab_size)} (the top-k kernel's k, the vocabulary) fit")
         fill = pad_token_id if pad_token_id is not None else 0
         rows = torch.arange(B, device=dev)
-        first = KVCache(cfg, B, T0 + n, dev, weight.dtype)
+        first = KVCache(cfg, B, T0 + n, dev, weight.dtype, kv_cache_dtype)
         h = base(ids, cache=first)[rows, lens - 1]  # one prefill per prompt
         first.set_lengths(lens)
         cache = first.repeat_rows(nb)

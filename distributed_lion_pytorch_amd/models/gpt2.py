@@ -91,18 +91,27 @@ class Attention(nn.Module):
         B, T, C = x.shape
         H, D = self.n_head, self.head_dim
         kc, vc = cache.layer(self.layer_idx)
+        ks, vs = cache.layer_scales(self.layer_idx)  # an fp8 cache: kc / vc are codes
         qkv = self.c_attn(x)
         if cache.prefilled and cache.chunk:
             q, k, v = (qkv[..., j * C:(j + 1) * C].view(B, T, H, D) for j in range(3))
-            q = fused.kv_append_chunk(q, k, v, cache.lengths, None, None, None, None, 0.0, kc, vc, cache.n_new)
+            q = fused.kv_append_chunk(q, k, v, cache.lengths, None, None, None, None, 0.0, kc, vc, cache.n_new, ks, vs)
+            if ks is not None:
+                return fused.cached_attention_fp8(q, kc, ks, vc, vs, cache.lengths, cache.n_new, 0, cache.width + T)
             return fused.chunk_attention(q, kc, vc, cache.kv_len, cache.n_new, 0, cache.width + T)
         if cache.prefilled:
             q, k, v = (qkv[:, 0, j * C:(j + 1) * C].view(B, H, D) for j in range(3))
-            q = fused.kv_append(q, k, v, cache.lengths, None, None, None, None, 0.0, kc, vc)
+            q = fused.kv_append(q, k, v, cache.lengths, None, None, None, None, 0.0, kc, vc, ks, vs)
+            if ks is not None:
+                return fused.cached_attention_fp8(q[:, None], kc, ks, vc, vs, cache.lengths, None, 0, cache.width + 1)
             return fused.decode_attention(q, kc, vc, cache.kv_len, 0, cache.width + 1).view(B, 1, C)
         q, k, v = (qkv[..., j * C:(j + 1) * C].view(B, T, H, D) for j in range(3))
-        kc[:, :T].copy_(k)
-        vc[:, :T].copy_(v)
+        if ks is not None:
+            fused.kv_quantize(k, kc, ks)
+            fused.kv_quantize(v, vc, vs)
+        else:
+            kc[:, :T].copy_(k)
+            vc[:, :T].copy_(v)
         return fused.causal_attention_gqa(q, k, v)
 
 

@@ -201,6 +201,7 @@ class LlamaAttention(nn.Module):
         fused.decode_attention reads the cache once for the whole group of query heads."""
         B, T, _ = x.shape
         kc, vc = cache.layer(self.layer_idx)
+        ks, vs = cache.layer_scales(self.layer_idx)  # an fp8 cache: kc / vc are codes
         q, k, v = _proj(x, (self.q_proj, self.k_proj, self.v_proj))
         gq, gk, eps = (self.q_norm.weight, self.k_norm.weight, self.q_norm.eps) if hasattr(self, "q_norm") else (None, None, 0.0)
         if cache.prefilled and cache.chunk:
@@ -208,15 +209,21 @@ class LlamaAttention(nn.Module):
             q = q.view(B, T, self.n_head, self.head_dim)
             k = k.view(B, T, self.n_kv, self.head_dim)
             v = v.view(B, T, self.n_kv, self.head_dim)
-            q = fused.kv_append_chunk(q, k, v, cache.lengths, cos, sin, gq, gk, eps, kc, vc, cache.n_new)
-            y = fused.chunk_attention(q, kc, vc, cache.kv_len, cache.n_new, self.window, cache.width + T)
+            q = fused.kv_append_chunk(q, k, v, cache.lengths, cos, sin, gq, gk, eps, kc, vc, cache.n_new, ks, vs)
+            if ks is not None:
+                y = fused.cached_attention_fp8(q, kc, ks, vc, vs, cache.lengths, cache.n_new, self.window, cache.width + T)
+            else:
+                y = fused.chunk_attention(q, kc, vc, cache.kv_len, cache.n_new, self.window, cache.width + T)
             return _lin(self.o_proj, y)
         if cache.prefilled:
             q = q[:, 0].view(B, self.n_head, self.head_dim)
             k = k[:, 0].view(B, self.n_kv, self.head_dim)
             v = v[:, 0].view(B, self.n_kv, self.head_dim)
-            q = fused.kv_append(q, k, v, cache.lengths, cos, sin, gq, gk, eps, kc, vc)
-            y = fused.decode_attention(q, kc, vc, cache.kv_len, self.window, cache.width + 1).view(B, 1, -1)
+            q = fused.kv_append(q, k, v, cache.lengths, cos, sin, gq, gk, eps, kc, vc, ks, vs)
+            if ks is not None:
+                y = fused.cached_attention_fp8(q[:, None], kc, ks, vc, vs, cache.lengths, None, self.window, cache.width + 1)
+            else:
+                y = fused.decode_attention(q, kc, vc, cache.kv_len, self.window, cache.width + 1).view(B, 1, -1)
             return _lin(self.o_proj, y)
         q = q.view(B, T, self.n_head, self.head_dim)
         k = k.view(B, T, self.n_kv, self.head_dim)
@@ -225,8 +232,12 @@ class LlamaAttention(nn.Module):
             q, k = fused.qk_norm_rope(q, gq, eps, cos, sin), fused.qk_norm_rope(k, gk, eps, cos, sin)
         else:
             q, k = fused.rope(q, cos, sin), fused.rope(k, cos, sin)
-        kc[:, :T].copy_(k)
-        vc[:, :T].copy_(v)
+        if ks is not None:
+            fused.kv_quantize(k, kc, ks)
+            fused.kv_quantize(v, vc, vs)
+        else:
+            kc[:, :T].copy_(k)
+            vc[:, :T].copy_(v)
         return _lin(self.o_proj, fused.causal_attention_gqa(q, k, v, 0.0, self.window))
 
 

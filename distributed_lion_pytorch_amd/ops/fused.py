@@ -1192,9 +1192,13 @@ def _rope_rows(x: torch.Tensor, c: torch.Tensor, s: torch.Tensor) -> torch.Tenso
     return x * c[:, None, :] + rot * s[:, None, :]
 
 
-def kv_append_reference(q, k, v, pos, cos, sin, q_gamma, k_gamma, eps, k_cache, v_cache) -> torch.Tensor:
+def kv_append_reference(q, k, v, pos, cos, sin, q_gamma, k_gamma, eps, k_cache, v_cache, k_scale=None,
+                        v_scale=None) -> torch.Tensor:
     """The PyTorch form of kv_append (same arguments): rope_reference / qk_norm_rope_reference at position
-    pos[b], then an indexed write of k and v into cache[b, pos[b]]."""
+    pos[b], then an indexed write of k and v into cache[b, pos[b]] (quantised by ``kv_quantize_reference`` when the
+    caches are fp8 codes with ``k_scale`` / ``v_scale``)."""
+    if k_scale is not None:
+        k_cache, v_cache = _QuantisingCache(k_cache, k_scale), _QuantisingCache(v_cache, v_scale)
     Tmax = k_cache.shape[1]
     p = pos.long()
     bad = ((p < 0) | (p >= Tmax)).any()
@@ -1219,17 +1223,29 @@ def kv_append_reference(q, k, v, pos, cos, sin, q_gamma, k_gamma, eps, k_cache, 
 
 
 def kv_append(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pos: torch.Tensor, cos, sin, q_gamma, k_gamma,
-              eps: float, k_cache: torch.Tensor, v_cache: torch.Tensor) -> torch.Tensor:
+              eps: float, k_cache: torch.Tensor, v_cache: torch.Tensor, k_scale=None, v_scale=None) -> torch.Tensor:
     """One decode step's q [B, H, D], k / v [B, Hkv, D] (column views of the fused q|k|v output are read in
     place): returns rope(norm(q)) [B, H, D] and writes rope(norm(k)) and v to ``cache[b, pos[b]]`` of the
     token-major caches [B, Tmax, Hkv, D].  ``pos`` int32 [B]; ``cos`` / ``sin`` [>= Tmax, D] or None (GPT-2: a
     pure append); ``q_gamma`` / ``k_gamma`` [D] or None (Qwen3 gains, ``eps``).  A position outside
     [0, Tmax) is clamped and raises through check_index_errors (on the CPU: at once).  The rotation and
-    the norm are bit for bit those of ``rope`` / ``qk_norm_rope`` at that position."""
+    the norm are bit for bit those of ``rope`` / ``qk_norm_rope`` at that position.  With ``k_scale`` / ``v_scale``
+    (fp32 [B, Tmax, Hkv]) the caches are fp8 codes (uint8): k and v are stored as ``kv_quantize_reference`` of the
+    bf16 rows the bf16 cache would hold; the returned q is the same bits."""
     if (cos is None) != (sin is None) or (q_gamma is None) != (k_gamma is None) or (q_gamma is not None and cos is None):
         raise ValueError("kv_append: cos / sin and q_gamma / k_gamma come as pairs, gains only with tables")
+    if (k_scale is None) != (v_scale is None):
+        raise ValueError("kv_append: k_scale and v_scale come as a pair")
     D = q.shape[-1]
     Tmax = k_cache.shape[1]
+    if k_scale is not None:
+        if _append8_ok(q, k, v, pos, cos, sin, q_gamma, k_gamma, k_cache, v_cache, k_scale, v_scale):
+            q, k, v = (t if _step_rows_ok(t) else t.contiguous() for t in (q, k, v))
+            if cos is not None:
+                cos, sin = cos.contiguous(), sin.contiguous()
+            return hip.ops().kv_append_fp8(q, k, v, pos.contiguous(), cos, sin, q_gamma, k_gamma, float(eps), k_cache,
+                                           v_cache, k_scale, v_scale, _index_flag(q.device))
+        return kv_append_reference(q, k, v, pos, cos, sin, q_gamma, k_gamma, eps, k_cache, v_cache, k_scale, v_scale)
     if (q.dtype == k.dtype == v.dtype == torch.bfloat16 and D in (64, 128) and q.is_cuda and pos.is_cuda
             and pos.dtype == torch.int32 and _cache_ok(k_cache) and _cache_ok(v_cache)
             and all(t is None or (t.dtype == torch.bfloat16 and t.shape[0] >= Tmax) for t in (cos, sin))
@@ -1328,9 +1344,13 @@ def chunk_positions(lengths: torch.Tensor, T: int, n_new, limit: int) -> torch.T
     return p.clamp(0, limit - 1)
 
 
-def kv_append_chunk_reference(q, k, v, pos, cos, sin, q_gamma, k_gamma, eps, k_cache, v_cache, n_new=None) -> torch.Tensor:
+def kv_append_chunk_reference(q, k, v, pos, cos, sin, q_gamma, k_gamma, eps, k_cache, v_cache, n_new=None,
+                              k_scale=None, v_scale=None) -> torch.Tensor:
     """The PyTorch form of kv_append_chunk (same arguments): rope_reference / qk_norm_rope_reference at the
-    positions pos[b] + t, then an indexed write of the tokens t < n_new[b] into cache[b, pos[b] + t]."""
+    positions pos[b] + t, then an indexed write of the tokens t < n_new[b] into cache[b, pos[b] + t] (quantised by
+    ``kv_quantize_reference`` when the caches are fp8 codes with ``k_scale`` / ``v_scale``)."""
+    if k_scale is not None:
+        k_cache, v_cache = _QuantisingCache(k_cache, k_scale), _QuantisingCache(v_cache, v_scale)
     B, T = q.shape[:2]
     Tmax = k_cache.shape[1]
     n = _chunk_counts(n_new, T, pos)
@@ -1366,18 +1386,33 @@ def kv_append_chunk_reference(q, k, v, pos, cos, sin, q_gamma, k_gamma, eps, k_c
 
 
 def kv_append_chunk(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pos: torch.Tensor, cos, sin, q_gamma, k_gamma,
-                    eps: float, k_cache: torch.Tensor, v_cache: torch.Tensor, n_new=None) -> torch.Tensor:
+                    eps: float, k_cache: torch.Tensor, v_cache: torch.Tensor, n_new=None, k_scale=None,
+                    v_scale=None) -> torch.Tensor:
     """``kv_append`` for T tokens per row: q [B, T, H, D], k / v [B, T, Hkv, D] (column views of the fused q|k|v
     output are read in place).  Token t of row b is normed / rotated at position ``pos[b] + t``; returns the
     rotated q [B, T, H, D] and writes k and v of the tokens ``t < n_new[b]`` (int32 [B], clamped into [0, T];
     None: all T) to ``cache[b, pos[b] + t]``.  The q rows of the other tokens are computed by the same
     arithmetic and mean nothing.  A written position outside [0, Tmax) is not written and raises through
     check_index_errors (on the CPU: at once).  The rotation and the norm are bit for bit those of ``rope`` /
-    ``qk_norm_rope`` at that position.  bf16 at head_dim 64 / 128 and T <= 8 runs csrc/chunk_attention.hip."""
+    ``qk_norm_rope`` at that position.  bf16 at head_dim 64 / 128 and T <= 8 runs csrc/chunk_attention.hip.
+    ``k_scale`` / ``v_scale``: the fp8 cache, as in ``kv_append``."""
     if (cos is None) != (sin is None) or (q_gamma is None) != (k_gamma is None) or (q_gamma is not None and cos is None):
         raise ValueError("kv_append_chunk: cos / sin and q_gamma / k_gamma come as pairs, gains only with tables")
+    if (k_scale is None) != (v_scale is None):
+        raise ValueError("kv_append_chunk: k_scale and v_scale come as a pair")
     T, D = q.shape[1], q.shape[-1]
     Tmax = k_cache.shape[1]
+    if k_scale is not None:
+        if (1 <= T <= CHUNK_MAX_TOKENS and (n_new is None or (n_new.is_cuda and n_new.dtype == torch.int32))
+                and _append8_ok(q, k, v, pos, cos, sin, q_gamma, k_gamma, k_cache, v_cache, k_scale, v_scale)):
+            q, k, v = (t if _chunk_rows_ok(t) else t.contiguous() for t in (q, k, v))
+            if cos is not None:
+                cos, sin = cos.contiguous(), sin.contiguous()
+            return hip.ops().kv_append_chunk_fp8(q, k, v, pos.contiguous(), None if n_new is None else n_new.contiguous(),
+                                                 cos, sin, q_gamma, k_gamma, float(eps), k_cache, v_cache, k_scale,
+                                                 v_scale, _index_flag(q.device))
+        return kv_append_chunk_reference(q, k, v, pos, cos, sin, q_gamma, k_gamma, eps, k_cache, v_cache, n_new, k_scale,
+                                         v_scale)
     if (q.dtype == k.dtype == v.dtype == torch.bfloat16 and D in (64, 128) and 1 <= T <= CHUNK_MAX_TOKENS and q.is_cuda
             and pos.is_cuda and pos.dtype == torch.int32 and _cache_ok(k_cache) and _cache_ok(v_cache)
             and (n_new is None or (n_new.is_cuda and n_new.dtype == torch.int32))
@@ -1444,6 +1479,109 @@ def chunk_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tenso
         return hip.ops().chunk_attention(q.contiguous(), k_cache, v_cache, kv_len.contiguous(),
                                          None if n_new is None else n_new.contiguous(), window, max_len, s, chunk)
     return chunk_attention_reference(q, k_cache, v_cache, kv_len, n_new, window, max_len)
+
+
+# ------------------------------------------------- generation on an fp8 (e4m3) KV cache (csrc/kv8.h, kv8_attention.hip)
+# codes uint8 [B, Tmax, Hkv, D] (torch.float8_e4m3fn bit patterns) and scales fp32 [B, Tmax, Hkv], one power of two
+# per (token, kv head); docs/DESIGN.md "FP8 KV cache" has the format.
+def kv_quantize_reference(x: torch.Tensor):
+    """(codes uint8 [..., D], scales fp32 [...]) of head rows x [..., D] -- the definition every writer follows:
+    ``e = ((bits(max|x|) + 0x00200000) >> 23) - 135`` clamped into [-126, 126] (max|x| / 2^e lies in [224, 448)
+    wherever e is not clamped), ``scale = 2^e``, ``code = e4m3_rne(float(x) * 2^-e)``.  x is rounded to bf16 first,
+    as the bf16 cache would store it."""
+    xf = x.to(torch.bfloat16).float()
+    a = xf.abs().amax(-1)
+    e = (((a.contiguous().view(torch.int32) + 0x00200000) >> 23) - 135).clamp(-126, 126)
+    scale = ((e + 127) << 23).view(torch.float32)
+    inv = ((127 - e) << 23).view(torch.float32)
+    codes = (xf * inv[..., None]).to(torch.float8_e4m3fn).view(torch.uint8)
+    return codes, scale
+
+
+def kv_dequantize(codes: torch.Tensor, scales: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
+    """codes [..., D] and scales [...] -> ``code * scale`` (exact in fp32)."""
+    return (codes.view(torch.float8_e4m3fn).float() * scales[..., None].float()).to(dtype)
+
+
+def _cache8_ok(c: torch.Tensor, s: torch.Tensor) -> bool:
+    if c.dim() != 4 or s.dim() != 3:
+        return False
+    B, Tmax, Hkv, D = c.shape
+    return (c.dtype == torch.uint8 and s.dtype == torch.float32 and tuple(s.shape) == (B, Tmax, Hkv) and c.is_cuda
+            and s.is_cuda and c.stride(3) == 1 and (Hkv == 1 or c.stride(2) == D)
+            and (Tmax == 1 or (c.stride(1) % 16 == 0 and c.stride(1) >= Hkv * D))
+            and (B == 1 or (c.stride(0) % 16 == 0 and c.stride(0) >= Tmax * c.stride(1))) and c.data_ptr() % 16 == 0
+            and (Hkv == 1 or s.stride(2) == 1) and (Tmax == 1 or s.stride(1) >= Hkv)
+            and (B == 1 or s.stride(0) >= Tmax * s.stride(1)))
+
+
+def kv_quantize(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor) -> None:
+    """The prefill's writer of an fp8 cache: x [B, T, Hkv, D] (the rotated k, or v; a column view of the fused
+    q|k|v output is read in place) -> ``codes[:, :T]`` and ``scales[:, :T]``, bit for bit ``kv_quantize_reference``.
+    bf16 at head_dim 64 / 128 runs csrc/kv8_attention.hip."""
+    B, T, Hkv, D = x.shape
+    if T > codes.shape[1]:
+        raise ValueError(f"kv_quantize: {T} tokens do not fit a cache of {codes.shape[1]}")
+    if x.dtype == torch.bfloat16 and D in (64, 128) and x.is_cuda and _cache8_ok(codes, scales) and _use_hip(x):
+        hip.ops().kv_quantize(x if _chunk_rows_ok(x) else x.contiguous(), codes, scales)
+        return
+    c, s = kv_quantize_reference(x)
+    codes[:, :T] = c
+    scales[:, :T] = s
+
+
+class _QuantisingCache:
+    """What the PyTorch forms of the appends write k or v into for an fp8 cache: an indexed assignment quantises."""
+
+    def __init__(self, codes, scales):
+        self.codes, self.scales, self.shape, self.dtype = codes, scales, codes.shape, torch.bfloat16
+
+    def __setitem__(self, idx, x):
+        self.codes[idx], self.scales[idx] = kv_quantize_reference(x)
+
+
+def _append8_ok(q, k, v, pos, cos, sin, q_gamma, k_gamma, k_cache, v_cache, k_scale, v_scale) -> bool:
+    Tmax = k_cache.shape[1]
+    return (q.dtype == k.dtype == v.dtype == torch.bfloat16 and q.shape[-1] in (64, 128) and q.is_cuda and pos.is_cuda
+            and pos.dtype == torch.int32 and _cache8_ok(k_cache, k_scale) and _cache8_ok(v_cache, v_scale)
+            and k_scale.stride() == v_scale.stride()
+            and all(t is None or (t.dtype == torch.bfloat16 and t.shape[0] >= Tmax) for t in (cos, sin))
+            and (q_gamma is None or all(g.dtype == torch.bfloat16 and g.is_contiguous() and g.data_ptr() % 16 == 0
+                                        for g in (q_gamma, k_gamma)))
+            and _use_hip(q))
+
+
+def cached_attention_fp8_reference(q, k_codes, k_scales, v_codes, v_scales, kv_len, n_new=None, window: int = 0,
+                                   max_len=None) -> torch.Tensor:
+    """The PyTorch form of cached_attention_fp8: ``kv_dequantize`` into ``chunk_attention_reference`` (whose masking
+    keeps whatever lies beyond a row's length, NaN codes and scales included, out of every product)."""
+    ct = torch.float64 if q.dtype == torch.float64 else torch.float32
+    return chunk_attention_reference(q, kv_dequantize(k_codes, k_scales, ct), kv_dequantize(v_codes, v_scales, ct), kv_len,
+                                     n_new, window, max_len)
+
+
+def cached_attention_fp8(q: torch.Tensor, k_codes: torch.Tensor, k_scales: torch.Tensor, v_codes: torch.Tensor,
+                         v_scales: torch.Tensor, kv_len: torch.Tensor, n_new=None, window: int = 0, max_len=None,
+                         splits=None) -> torch.Tensor:
+    """``chunk_attention`` on an fp8 cache: q [B, T, H, D] (T = 1..8 new queries per row, their keys already appended),
+    codes [B, Tmax, Hkv, D] uint8 and scales [B, Tmax, Hkv] fp32 of k and v, kv_len int32 [B] (the lengths before these
+    T tokens) -> [B, T, H * D].  ``n_new`` / ``window`` / ``max_len`` / ``splits`` mean what they mean there; T = 1
+    with ``n_new=None`` is the decode step (``decode_attention`` with ``kv_len + 1``).  bf16 q at head_dim 64 / 128
+    with H / Hkv in 1..8 runs csrc/kv8_attention.hip (the chunk kernel's grid, partials and MFMA arithmetic on
+    dequantised operands, the scales folded into the scores and into P; no atomics); anything else the PyTorch form."""
+    B, T, H, D = q.shape
+    Tmax, Hkv = k_codes.shape[1], k_codes.shape[2]
+    window = int(window or 0)
+    max_len = Tmax if max_len is None else max(1, min(int(max_len), Tmax))
+    if (q.dtype == torch.bfloat16 and D in (64, 128) and 1 <= T <= CHUNK_MAX_TOKENS and H % Hkv == 0
+            and 1 <= H // Hkv <= 8 and q.is_cuda and kv_len.is_cuda and kv_len.dtype == torch.int32
+            and (n_new is None or (n_new.is_cuda and n_new.dtype == torch.int32)) and window < (1 << 30)
+            and _cache8_ok(k_codes, k_scales) and _cache8_ok(v_codes, v_scales) and B <= 65535 and Hkv <= 65535
+            and _use_hip(q)):
+        s, chunk = chunk_splits(B, Hkv, max_len, T, window, splits)
+        return hip.ops().cached_attention_fp8(q.contiguous(), k_codes, k_scales, v_codes, v_scales, kv_len.contiguous(),
+                                              None if n_new is None else n_new.contiguous(), window, max_len, s, chunk)
+    return cached_attention_fp8_reference(q, k_codes, k_scales, v_codes, v_scales, kv_len, n_new, window, max_len)
 
 
 # ------------------------------------------------- generation: the M <= 16 projections (csrc/skinny_gemm.hip)

@@ -114,6 +114,40 @@ def kernel_table(dev, iters):
     return lines
 
 
+def kv8_table(dev, iters, chunks=(1, 5, 8)):
+    """cached_attention_fp8 on an fp8 cache against the bf16 kernels on a bf16 cache of the same shape: decode_attention
+    at T = 1, chunk_attention at T = 5 / 8; every row's last query sees ``len`` keys.  Both rotate over the same number
+    of cache buffers (sized by the bf16 bytes: more than 256 MiB for the fp8 caches too)."""
+    lines = [f"{'B':>3s} {'H':>3s} {'Hkv':>3s} {'D':>4s} {'len':>5s} {'T':>2s} {'bf16 us':>9s} {'TB/s':>6s} {'fp8 us':>9s} "
+             f"{'TB/s':>6s} {'fp8 / bf16 time':>15s} {'bytes ratio':>11s}"]
+    for B, H, Hkv, D, L in KERNEL_SHAPES:
+        bytes16 = 2 * B * Hkv * L * D * 2
+        bytes8 = 2 * B * Hkv * L * (D + 4)
+        n = max(2, min(64, -(-3 * CACHE_BYTES // bytes16)))
+        g = torch.Generator(device=dev).manual_seed(0)
+        caches = [torch.randn(2, B, L, Hkv, D, device=dev, dtype=torch.bfloat16, generator=g) for _ in range(n)]
+        codes = [torch.empty(2, B, L, Hkv, D, device=dev, dtype=torch.uint8) for _ in range(n)]
+        scales = [torch.empty(2, B, L, Hkv, device=dev, dtype=torch.float32) for _ in range(n)]
+        for c16, c8, s8 in zip(caches, codes, scales):
+            for j in range(2):
+                fused.kv_quantize(c16[j], c8[j], s8[j])
+        for T in chunks:
+            q = torch.randn(B, T, H, D, device=dev, dtype=torch.bfloat16, generator=g)
+            before = torch.full((B,), L - T, dtype=torch.int32, device=dev)
+            full = torch.full((B,), L, dtype=torch.int32, device=dev)
+            if T == 1:
+                t16 = _time(lambda i: fused.decode_attention(q[:, 0], caches[i][0], caches[i][1], full, 0, L), n, iters)
+            else:
+                t16 = _time(lambda i: fused.chunk_attention(q, caches[i][0], caches[i][1], before, None, 0, L), n, iters)
+            t8 = _time(lambda i: fused.cached_attention_fp8(q, codes[i][0], scales[i][0], codes[i][1], scales[i][1], before,
+                                                            None, 0, L), n, iters)
+            lines.append(f"{B:3d} {H:3d} {Hkv:3d} {D:4d} {L:5d} {T:2d} {t16 * 1e6:9.1f} {bytes16 / t16 / 1e12:6.2f} "
+                         f"{t8 * 1e6:9.1f} {bytes8 / t8 / 1e12:6.2f} {t8 / t16:15.2f} {bytes8 / bytes16:11.2f}")
+        del caches, codes, scales
+        torch.cuda.empty_cache()
+    return lines
+
+
 # ------------------------------------------------------------------------------------------ skinny-M GEMMs
 # [N, K] of a decode step's weight GEMMs: Llama-3-8B (q|k|v, o, gate|up, down, LM head), GPT-2 (c_attn, c_proj, c_fc,
 # mlp c_proj, LM head), Qwen2-0.5B's down_proj (K = 64 x 76)
@@ -430,6 +464,9 @@ def main(argv=None):
     ap.add_argument("--num_beams", type=int, default=1,
                     help="end to end: beam search at B / num_beams prompts next to greedy at B rows, instead of the "
                          "generate / naive-loop / phase report")
+    ap.add_argument("--kv_cache_dtype", default=None, choices=("fp8_e4m3",),
+                    help="the kernel table's fp8 axis: cached_attention_fp8 (csrc/kv8_attention.hip) at T = 1 / 5 / 8 "
+                         "against decode_attention / chunk_attention on a bf16 cache of the same shape")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("bench_decode.py measures on the GPU; there is none here")
@@ -440,6 +477,12 @@ def main(argv=None):
         report += ["## decode_attention, bf16, every row at full length; K+V bytes over kernel time against the "
                    f"{HBM_COPY_TBS} TB/s float4 copy", ""] + kernel_table(dev, a.iters) + [""]
         print("\n".join(report), flush=True)
+    if a.kv_cache_dtype == "fp8_e4m3":
+        head = ["## cached_attention_fp8 on an fp8 (e4m3) cache against the bf16 kernels on a bf16 cache, every row at "
+                "full length; K+V bytes (codes and scales for fp8) over kernel time", ""]
+        print("\n".join(head), flush=True)
+        report += head + kv8_table(dev, a.iters) + [""]
+        print("\n".join(report[-len(KERNEL_SHAPES) * 3 - 2:]), flush=True)
     if not a.skip_skinny:
         head = ["## skinny-M GEMM (csrc/skinny_gemm.hip), weight bytes over device time (summed kernel durations of a "
                 f"profiler trace) against the {HBM_COPY_TBS} TB/s float4 copy; 4-bit bytes are {W4_BYTES} per element", ""]
