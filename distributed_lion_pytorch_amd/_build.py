@@ -75,8 +75,9 @@ def _flags():
 # slower than two plain ops beside MFMAs (dQ 88 -> 86 us at the GPT-2 shape)
 EXTRA_FLAGS = {
     "attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],
-    # no packed fp32 arithmetic (v_pk_mul_f32 and kin) in the fp8-cache kernels: plain VALU ops only
+    # no packed fp32 arithmetic (v_pk_mul_f32 and kin) in the fp8-cache and extend kernels: plain VALU ops only
     "kv8_attention.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "extend_attention.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

@@ -1504,7 +1504,7 @@ Tensor kv_append_chunk(const Tensor& q, const Tensor& k, const Tensor& v, const 
   TORCH_CHECK(q.dim() == 4, "dlion kv_append_chunk: q must be [B, T, H, D]");
   const int64_t B = q.size(0), T = q.size(1), H = q.size(2), D = q.size(3);
   TORCH_CHECK(D == 64 || D == 128, "dlion kv_append_chunk: head_dim must be 64 or 128");
-  TORCH_CHECK(T >= 1 && T <= dlion::kChunkMaxTokens, "dlion kv_append_chunk: T must be in [1, 8]");
+  TORCH_CHECK(T >= 1, "dlion kv_append_chunk: T must be >= 1");
   TORCH_CHECK(k.dim() == 4 && v.dim() == 4 && k.size(2) == v.size(2), "dlion kv_append_chunk: k / v must be [B, T, Hkv, D]");
   const int64_t Hkv = k.size(2);
   check_chunk_rows("kv_append_chunk", "q", q, B, T, D);
@@ -1587,6 +1587,53 @@ Tensor chunk_attention(const Tensor& q, const Tensor& k_cache, const Tensor& v_c
             "chunk_attention");
   return out;
 }
+
+// out [B, T, H D], any T; splits / chunk from ops/fused.py extend_splits (a host rule over B, Hkv, max_len, T, window)
+Tensor extend_attention(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const Tensor& kv_len,
+                        const std::optional<Tensor>& n_new, int64_t window, int64_t max_len, int64_t splits,
+                        int64_t chunk) {
+  TORCH_CHECK(q.dim() == 4 && k_cache.dim() == 4,
+              "dlion extend_attention: q must be [B, T, H, D], the caches [B, Tmax, Hkv, D]");
+  const int64_t B = q.size(0), T = q.size(1), H = q.size(2), D = q.size(3), Tmax = k_cache.size(1), Hkv = k_cache.size(2);
+  TORCH_CHECK(D == 64 || D == 128, "dlion extend_attention: head_dim must be 64 or 128");
+  TORCH_CHECK(T >= 1 && T < (int64_t{1} << 31), "dlion extend_attention: T must be >= 1");
+  TORCH_CHECK(Hkv >= 1 && H % Hkv == 0 && H / Hkv <= 8, "dlion extend_attention: H / Hkv must be an integer in [1, 8]");
+  TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16 && q.is_contiguous() &&
+                  reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0,
+              "dlion extend_attention: q must be a contiguous, 16-byte aligned bf16 GPU tensor");
+  check_cache("extend_attention", "k_cache", k_cache, B, Hkv, D);
+  check_cache("extend_attention", "v_cache", v_cache, B, Hkv, D);
+  TORCH_CHECK(v_cache.size(1) == Tmax, "dlion extend_attention: the caches differ in length");
+  TORCH_CHECK(kv_len.is_cuda() && kv_len.scalar_type() == at::kInt && kv_len.is_contiguous() && kv_len.numel() == B,
+              "dlion extend_attention: kv_len must be a contiguous int32 [B] GPU tensor");
+  const int* nn = chunk_n_new("extend_attention", n_new, B);
+  TORCH_CHECK(max_len >= 1 && max_len < (int64_t{1} << 31) && window >= 0 && window < (int64_t{1} << 30) &&
+                  splits >= 1 && splits <= dlion::kDecodeMaxSplits && chunk >= 1 && chunk < (int64_t{1} << 31) &&
+                  B <= 65535 && Hkv <= 65535 && B * T * H < (int64_t{1} << 31),
+              "dlion extend_attention: bad max_len / window / splits / chunk / batch");
+  const c10::DeviceGuard dg(q.device());
+  auto out = at::empty({B, T, H * D}, q.options());
+  Tensor part_ml, part_o;
+  float *pm = nullptr, *pl = nullptr, *po = nullptr;
+  if (splits > 1) {  // one split stores bf16 from the kernel
+    const auto f32 = q.options().dtype(at::kFloat);
+    part_ml = at::empty({2, B, T, H, splits}, f32);
+    part_o = at::empty({B, T, H, splits, D}, f32);
+    pm = part_ml.data_ptr<float>();
+    pl = pm + B * T * H * splits;
+    po = part_o.data_ptr<float>();
+  }
+  check_hip(dlion::launch_extend_attention(
+                q.data_ptr(), k_cache.data_ptr(), cache_batch_stride(k_cache), cache_token_stride(k_cache),
+                v_cache.data_ptr(), cache_batch_stride(v_cache), cache_token_stride(v_cache), kv_len.data_ptr<int>(), nn,
+                pm, pl, po, out.data_ptr(), static_cast<int>(B), static_cast<int>(T), static_cast<int>(H),
+                static_cast<int>(Hkv), static_cast<int>(D), static_cast<int>(Tmax), static_cast<int>(max_len),
+                static_cast<int>(window), static_cast<int>(splits), static_cast<int>(chunk),
+                1.0f / std::sqrt(static_cast<float>(D)), cur_stream()),
+            "extend_attention");
+  return out;
+}
+
 // ---- generation on an fp8 KV cache (csrc/kv8_attention.hip, the fp8 appends of decode.hip / chunk_attention.hip)
 // codes [B, Tmax, Hkv, D] uint8, token-major with contiguous heads and 16-byte aligned token / batch strides;
 // scales [B, Tmax, Hkv] fp32 with contiguous heads
@@ -1853,6 +1900,8 @@ TORCH_LIBRARY(dlion, m) {
         " Tensor? q_gamma, Tensor? k_gamma, float eps, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor(c!) err) -> Tensor");
   m.def("chunk_attention(Tensor q, Tensor k_cache, Tensor v_cache, Tensor kv_len, Tensor? n_new, int window,"
         " int max_len, int splits, int chunk) -> Tensor");
+  m.def("extend_attention(Tensor q, Tensor k_cache, Tensor v_cache, Tensor kv_len, Tensor? n_new, int window,"
+        " int max_len, int splits, int chunk) -> Tensor");
   m.def("kv_quantize(Tensor x, Tensor(a!) codes, Tensor(b!) scales) -> ()");
   m.def("kv_append_fp8(Tensor q, Tensor k, Tensor v, Tensor pos, Tensor? cos, Tensor? sin, Tensor? q_gamma,"
         " Tensor? k_gamma, float eps, Tensor(a!) k_codes, Tensor(b!) v_codes, Tensor(c!) k_scales, Tensor(d!) v_scales,"
@@ -2002,6 +2051,7 @@ TORCH_LIBRARY_IMPL(dlion, CUDA, m) {
   m.impl("decode_attention", &decode_attention);
   m.impl("kv_append_chunk", &kv_append_chunk);
   m.impl("chunk_attention", &chunk_attention);
+  m.impl("extend_attention", &extend_attention);
   m.impl("kv_quantize", &kv_quantize);
   m.impl("kv_append_fp8", &kv_append_fp8);
   m.impl("kv_append_chunk_fp8", &kv_append_chunk_fp8);

@@ -350,7 +350,14 @@ hipError_t launch_chunk_attention(const void* q, const void* k_cache, int64_t k_
 #undef DLION_CHUNK
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  const dim3 cgrid(static_cast<unsigned>(B * T * H));
+  return launch_chunk_combine(part_m, part_l, part_o, out, static_cast<int64_t>(B) * T * H, D, splits, st);
+}
+
+hipError_t launch_chunk_combine(const float* part_m, const float* part_l, const float* part_o, void* out,
+                                int64_t rows, int D, int splits, hipStream_t st) {
+  if (rows <= 0) return hipSuccess;
+  if ((D != 64 && D != 128) || splits < 1 || rows > 0x7fffffff) return hipErrorInvalidValue;
+  const dim3 cgrid(static_cast<unsigned>(rows));
   if (D == 128)
     hipLaunchKernelGGL(chunk_combine_kernel<128>, cgrid, dim3(128), 0, st, part_m, part_l, part_o,
                        static_cast<uint16_t*>(out), splits);

@@ -223,6 +223,21 @@ hipError_t launch_chunk_attention(const void* q, const void* k_cache, int64_t k_
                                   const int* n_new, float* part_m, float* part_l, float* part_o, void* out, int B,
                                   int T, int H, int Hkv, int D, int Tmax, int max_len, int window, int splits,
                                   int chunk, float scale, hipStream_t st);
+// the combine pass of the partials above over `rows` = B T H query rows: out [rows, D] bf16, index order
+hipError_t launch_chunk_combine(const float* part_m, const float* part_l, const float* part_o, void* out,
+                                int64_t rows, int D, int splits, hipStream_t st);
+
+// ---- generation, any T tokens per sequence (extend_attention.hip); bf16, D in {64, 128}
+// launch_chunk_attention's semantics without its limit on T.  A block owns kExtendTQ consecutive tokens of one kv
+// head and one key split; splits blocks of chunk keys per (token tile, kv head, row), splits chunk >=
+// min(window + kExtendTQ - 1, max_len).  splits == 1 writes out directly (the partials may be null); otherwise
+// the partials have launch_chunk_attention's layout and launch_chunk_combine reduces them.
+constexpr int kExtendTQ = 16;
+hipError_t launch_extend_attention(const void* q, const void* k_cache, int64_t k_bs, int64_t k_ts,
+                                   const void* v_cache, int64_t v_bs, int64_t v_ts, const int* kv_len,
+                                   const int* n_new, float* part_m, float* part_l, float* part_o, void* out, int B,
+                                   int T, int H, int Hkv, int D, int Tmax, int max_len, int window, int splits,
+                                   int chunk, float scale, hipStream_t st);
 
 // ---- generation on an fp8 KV cache (kv8.h, kv8_attention.hip; the appends in decode.hip / chunk_attention.hip)
 // The cache: codes uint8 [B, Tmax, Hkv, D] (OCP e4m3fn; batch / token strides in bytes, heads contiguous, 16-byte

@@ -5,7 +5,8 @@ k and v in, so the prefill writes them with plain copies -- and the per-row leng
 take it as an optional ``cache`` argument (models/llama.py, models/gpt2.py): the first call is the prefill (the
 prompt through the flash forward), every later call one decode step (one token per row through
 ``fused.kv_append`` and ``fused.decode_attention``, csrc/decode.hip) or a chunk of up to 8 tokens per row, ragged
-by ``n_new`` (``fused.kv_append_chunk`` and ``fused.chunk_attention``, csrc/chunk_attention.hip);
+by ``n_new`` (``fused.kv_append_chunk`` and ``fused.chunk_attention``, csrc/chunk_attention.hip), or with
+``extend=True`` any number of tokens per row (``fused.extend_attention``, csrc/extend_attention.hip);
 ``KVCache.truncate`` rolls rows back.
 
 ``KVCache(..., kv_dtype="fp8_e4m3")`` (``generate(kv_cache_dtype="fp8_e4m3")``) holds e4m3 codes and one power-of-two
@@ -96,10 +97,11 @@ class KVCache:
             return None, None
         return self._scales[i, 0], self._scales[i, 1]
 
-    def begin(self, B: int, T: int, n_new: Optional[torch.Tensor] = None) -> bool:
+    def begin(self, B: int, T: int, n_new: Optional[torch.Tensor] = None, extend: bool = False) -> bool:
         """Start a forward of T tokens per row; True for the prefill (the first call).  After the prefill T = 1
         is a decode step and 1 < T <= 8 a chunk (``fused.kv_append_chunk`` / ``fused.chunk_attention``), of
-        which row b keeps the first ``n_new[b]`` tokens ([B], 0 <= n_new[b] <= T; None: all T)."""
+        which row b keeps the first ``n_new[b]`` tokens ([B], 0 <= n_new[b] <= T; None: all T).  ``extend``
+        accepts any T >= 1 that fits (``fused.extend_attention``: a new turn, a prompt prefilled in pieces)."""
         if B != self.batch:
             raise ValueError(f"KVCache: built for batch {self.batch}, got {B}")
         if torch.is_grad_enabled():
@@ -110,8 +112,9 @@ class KVCache:
             if T > self.max_len:
                 raise ValueError(f"KVCache: a prompt of {T} tokens does not fit max_len {self.max_len}")
             return True
-        if not 1 <= T <= fused.CHUNK_MAX_TOKENS:
-            raise ValueError(f"KVCache: after the prefill a forward takes 1 to {fused.CHUNK_MAX_TOKENS} tokens per row")
+        if T < 1 or (T > fused.CHUNK_MAX_TOKENS and not extend):
+            raise ValueError(f"KVCache: after the prefill a forward takes 1 to {fused.CHUNK_MAX_TOKENS} tokens per row"
+                             " (more with extend=True)")
         if self.width + T > self.max_len:
             raise ValueError(f"KVCache: full ({self.max_len} positions)")
         self.chunk = T > 1 or n_new is not None
@@ -246,7 +249,8 @@ class NativeGenerateMixin:
                  top_p: float = 1.0, eos_token_id=None, pad_token_id: Optional[int] = None,
                  seed: Optional[int] = None, num_beams: int = 1, num_return_sequences: int = 1,
                  length_penalty: float = 1.0, early_stopping: bool = False, return_dict_in_generate: bool = False,
-                 assistant_model=None, num_assistant_tokens: int = 5, kv_cache_dtype: Optional[str] = None):
+                 assistant_model=None, num_assistant_tokens: int = 5, kv_cache_dtype: Optional[str] = None,
+                 prefill_chunk_size: Optional[int] = None):
         """[B, T0] prompts -> [B, T0 + n_new] long: the prompt exactly as given, then the new tokens.
 
         Greedy takes the top-1 of ``fused.lm_head_score`` (the lowest id on ties, no [B, V] tensor); sampling
@@ -275,7 +279,17 @@ class NativeGenerateMixin:
         128, 0.53 at 64).  Only what is cached is quantised -- the prompt's own attention in the prefill runs on the
         unquantised k and v, q and the probabilities stay bf16 / fp32 -- so the tokens may differ from the bf16
         cache's wherever two logits are closer than the quantisation error.  With ``assistant_model`` this model's
-        cache takes the type and the assistant's stays in its own dtype.  Default None: the model's dtype."""
+        cache takes the type and the assistant's stays in its own dtype.  Default None: the model's dtype.
+
+        ``prefill_chunk_size=N`` prefills the prompt in pieces, which bounds the prefill's activation memory by N
+        columns: the flash forward of the first N columns, then forwards of N columns each on the cache
+        (``extend=True``: ``fused.kv_append_chunk`` and ``fused.extend_attention``), ragged prompts by ``n_new``; every
+        row's last hidden state is taken from the piece it falls in.  It applies to greedy decoding, sampling, beam
+        search and the target of ``assistant_model``.  Default None: one prefill of the whole prompt."""
+        if prefill_chunk_size is not None:
+            prefill_chunk_size = int(prefill_chunk_size)
+            if prefill_chunk_size < 1:
+                raise ValueError(f"generate: prefill_chunk_size must be >= 1, got {prefill_chunk_size}")
         if kv_cache_dtype not in KV_CACHE_DTYPES:
             raise ValueError(f"generate: kv_cache_dtype must be one of {KV_CACHE_DTYPES}, got {kv_cache_dtype!r}")
         num_beams, num_return_sequences = int(num_beams), int(num_return_sequences)
@@ -333,13 +347,14 @@ class NativeGenerateMixin:
         weight = self.lm_head.weight
         if assistant_model is not None:
             out = self._speculative(assistant_model, input_ids, ids, lens, max_new_tokens, eos, pad_token_id, k,
-                                    kv_cache_dtype)
+                                    kv_cache_dtype, prefill_chunk_size)
             fused.check_index_errors()
             return out if return_dict_in_generate else out.sequences
         if num_beams > 1:
             lo = T0 if attention_mask is None else int(lens.min())
             out = self._beam_search(input_ids, ids, lens, lo, max_new_tokens, eos, pad_token_id, num_beams,
-                                    num_return_sequences, float(length_penalty), early_stopping, kv_cache_dtype)
+                                    num_return_sequences, float(length_penalty), early_stopping, kv_cache_dtype,
+                                    prefill_chunk_size)
             fused.check_index_errors()
             return out if return_dict_in_generate else out.sequences
         cache = KVCache(cfg, B, total, dev, weight.dtype, kv_cache_dtype)
@@ -349,9 +364,7 @@ class NativeGenerateMixin:
             gen.manual_seed(int(seed))
 
         base = self._decoder()
-        rows = torch.arange(B, device=dev)
-        h = base(ids, cache=cache)[rows, lens - 1]  # prefill: the hidden state of every row's last real token
-        cache.set_lengths(lens)
+        h = self._prefill(base, ids, lens, cache, prefill_chunk_size)
         new = torch.empty(B, max_new_tokens, dtype=torch.long, device=dev)
         finished = torch.zeros(B, dtype=torch.bool, device=dev)
         done_at = torch.full((B,), max_new_tokens, dtype=torch.long, device=dev)  # the step a row emitted EOS at
@@ -382,7 +395,31 @@ class NativeGenerateMixin:
         out = torch.cat([input_ids, new[:, :n_new]], dim=1)
         return GenerateOutput(out, None) if return_dict_in_generate else out
 
-    def _speculative(self, assistant, input_ids, ids, lens, n, eos, pad_token_id, k, kv_cache_dtype=None):
+    @staticmethod
+    def _prefill(base, ids, lens, cache, piece=None):
+        """The prompt into a fresh cache: the hidden state [B, C] of every row's last real token, the cache's lengths
+        set to ``lens``.  ``piece`` (generate's ``prefill_chunk_size``): the flash forward of the first ``piece``
+        columns, then extend forwards of ``piece`` columns each, of which row b keeps ``clamp(lens[b] - offset, 0,
+        piece)``; None, or a prompt no wider than ``piece``: one forward of the whole prompt."""
+        B, T0 = ids.shape
+        rows = torch.arange(B, device=ids.device)
+        if piece is None or piece >= T0:
+            h = base(ids, cache=cache)[rows, lens - 1]
+            cache.set_lengths(lens)
+            return h
+        last = lens - 1
+        h = base(ids[:, :piece], cache=cache)[rows, last.clamp_max(piece - 1)]
+        cache.set_lengths(lens.clamp_max(piece))
+        for off in range(piece, T0, piece):
+            cols = ids[:, off:off + piece]
+            w = cols.shape[1]
+            hp = base(cols, cache=cache, n_new=(lens - off).clamp(0, w).to(torch.int32), extend=True)
+            here = (last >= off) & (last < off + w)
+            h = torch.where(here[:, None], hp[rows, (last - off).clamp(0, w - 1)], h)
+        return h
+
+    def _speculative(self, assistant, input_ids, ids, lens, n, eos, pad_token_id, k, kv_cache_dtype=None,
+                     prefill_chunk_size=None):
         """Greedy speculative decoding.  Row b has emitted ``count[b]`` tokens, the last of which (``last``) is not
         in the target's cache yet; the assistant's cache lacks the last one or two of them (``unseen``: two when
         every draft of the previous round was accepted, since the last draft was never fed to the assistant).  A
@@ -401,8 +438,7 @@ class NativeGenerateMixin:
         rows = torch.arange(B, device=dev)
         cache = KVCache(cfg, B, size, dev, weight.dtype, kv_cache_dtype)
         a_cache = KVCache(acfg, B, size, dev, a_weight.dtype)
-        h = base(ids, cache=cache)[rows, lens - 1]
-        cache.set_lengths(lens)
+        h = self._prefill(base, ids, lens, cache, prefill_chunk_size)
         a_base(ids, cache=a_cache)
         a_cache.set_lengths(lens)
 
@@ -475,7 +511,7 @@ class NativeGenerateMixin:
         return SpeculativeOutput(out, None, rounds, accepted)
 
     def _beam_search(self, input_ids, ids, lens, lo, n, eos, pad_token_id, nb, n_ret, length_penalty, early_stopping,
-                     kv_cache_dtype=None):
+                     kv_cache_dtype=None, prefill_chunk_size=None):
         """transformers' ``GenerationMixin._beam_search`` on the native cache: the same running / finished beam
         sets, scores and stopping rules, with two differences in mechanics.  The candidates of a step are the
         ``keep`` best continuations of every beam (``fused.lm_head_topk``: values - logsumexp are the
@@ -493,8 +529,7 @@ class NativeGenerateMixin:
         fill = pad_token_id if pad_token_id is not None else 0
         rows = torch.arange(B, device=dev)
         first = KVCache(cfg, B, T0 + n, dev, weight.dtype, kv_cache_dtype)
-        h = base(ids, cache=first)[rows, lens - 1]  # one prefill per prompt
-        first.set_lengths(lens)
+        h = self._prefill(base, ids, lens, first, prefill_chunk_size)  # one prefill per prompt
         cache = first.repeat_rows(nb)
         del first
         h = h.repeat_interleave(nb, dim=0)

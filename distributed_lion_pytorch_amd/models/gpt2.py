@@ -74,20 +74,21 @@ class Attention(nn.Module):
         self.c_proj = Conv1D(cfg.n_embd, cfg.n_embd)
         self.attn_pdrop = cfg.attn_pdrop
 
-    def forward(self, x, proj_bias: bool = True, cache=None):
+    def forward(self, x, proj_bias: bool = True, cache=None, extend: bool = False):
         """proj_bias=False leaves c_proj's bias to the caller's fused
         residual+dropout+LayerNorm kernel (its gradient comes out of it too)."""
         if cache is not None:
-            y = self._attend_cached(x, cache)
+            y = self._attend_cached(x, cache, extend)
             return self.c_proj(y) if proj_bias else linear_kn(y, self.c_proj.weight, None)
         y = fused.qkv_attention(x, self.c_attn.weight, self.c_attn.bias, self.n_head,
                                 self.attn_pdrop if self.training else 0.0)  # [B, T, C]
         return self.c_proj(y) if proj_bias else linear_kn(y, self.c_proj.weight, None)
 
-    def _attend_cached(self, x, cache):
+    def _attend_cached(self, x, cache, extend: bool = False):
         """Generation (models/generation.py KVCache): the packed qkv split into its q | k | v column views.
         Prefill: k and v copied into cache[:, :T], attention by the flash forward.  Decode step: a pure append
-        (no rotary tables) and fused.decode_attention over the cache; a chunk of T tokens per row: their chunk forms."""
+        (no rotary tables) and fused.decode_attention over the cache; a chunk of T tokens per row: their chunk forms
+        (``extend``: any T, fused.extend_attention above 8 tokens per row)."""
         B, T, C = x.shape
         H, D = self.n_head, self.head_dim
         kc, vc = cache.layer(self.layer_idx)
@@ -98,6 +99,8 @@ class Attention(nn.Module):
             q = fused.kv_append_chunk(q, k, v, cache.lengths, None, None, None, None, 0.0, kc, vc, cache.n_new, ks, vs)
             if ks is not None:
                 return fused.cached_attention_fp8(q, kc, ks, vc, vs, cache.lengths, cache.n_new, 0, cache.width + T)
+            if extend:
+                return fused.extend_attention(q, kc, vc, cache.kv_len, cache.n_new, 0, cache.width + T)
             return fused.chunk_attention(q, kc, vc, cache.kv_len, cache.n_new, 0, cache.width + T)
         if cache.prefilled:
             q, k, v = (qkv[:, 0, j * C:(j + 1) * C].view(B, H, D) for j in range(3))
@@ -167,9 +170,9 @@ class GPT2Model(nn.Module):
         self.embd_pdrop = cfg.embd_pdrop
         self.gradient_checkpointing = False
 
-    def forward(self, input_ids, cache=None, n_new=None):
+    def forward(self, input_ids, cache=None, n_new=None, extend: bool = False):
         if cache is not None:
-            return self._forward_cached(input_ids, cache, n_new)
+            return self._forward_cached(input_ids, cache, n_new, extend)
         p = self.embd_pdrop if self.training else 0.0
         x = fused.embed(input_ids, self.wte.weight, self.wpe.weight, p)  # gather + add + dropout, one kernel
         if self.gradient_checkpointing and self.training:
@@ -190,12 +193,13 @@ class GPT2Model(nn.Module):
                                           bias=blk.mlp.c_proj.bias)
         return h
 
-    def _forward_cached(self, input_ids, cache, n_new=None):
+    def _forward_cached(self, input_ids, cache, n_new=None, extend: bool = False):
         """The prefill (first call on a fresh KVCache: the whole prompt), one decode step (one token per row, at
-        position lengths[b]) or a chunk (up to 8 tokens per row at the positions lengths[b] + t, of which row b
-        keeps ``n_new[b]``) of generation, through the fused chain of ``forward`` without dropout."""
+        position lengths[b]) or a chunk (up to 8 tokens per row, any number with ``extend``, at the positions
+        lengths[b] + t, of which row b keeps ``n_new[b]``) of generation, through the fused chain of ``forward``
+        without dropout."""
         B, T = input_ids.shape
-        if cache.begin(B, T, n_new):
+        if cache.begin(B, T, n_new, extend):
             x = fused.embed(input_ids, self.wte.weight, self.wpe.weight, 0.0)
         elif cache.chunk:
             pos = fused.chunk_positions(cache.lengths, T, cache.n_new, self.wpe.weight.shape[0])
@@ -205,8 +209,8 @@ class GPT2Model(nn.Module):
         first = self.h[0].ln_1
         h = fused.norm(x, first.weight, first.bias, first.eps)
         for i, blk in enumerate(self.h):
-            x, h = fused.dropout_add_norm(blk.attn(h, proj_bias=False, cache=cache), x, blk.ln_2.weight, blk.ln_2.bias,
-                                          blk.ln_2.eps, 0.0, bias=blk.attn.c_proj.bias)
+            x, h = fused.dropout_add_norm(blk.attn(h, proj_bias=False, cache=cache, extend=extend), x, blk.ln_2.weight,
+                                          blk.ln_2.bias, blk.ln_2.eps, 0.0, bias=blk.attn.c_proj.bias)
             nxt = self.h[i + 1].ln_1 if i + 1 < len(self.h) else self.ln_f
             x, h = fused.dropout_add_norm(blk.mlp(h, proj_bias=False), x, nxt.weight, nxt.bias, nxt.eps, 0.0,
                                           bias=blk.mlp.c_proj.bias)
@@ -272,9 +276,11 @@ class GPT2LMHeadModel(NativeGenerateMixin, LossOptionsMixin, PreTrainedModel):
         self.transformer.gradient_checkpointing = False
 
     def forward(self, input_ids=None, labels=None, attention_mask=None, num_items_in_batch=None,
-                return_dict: Optional[bool] = None, predictions: bool = False, cache=None, **kwargs):
-        # cache (models/generation.py KVCache): the prefill or one decode step of generation
-        h = self.transformer(input_ids, cache)
+                return_dict: Optional[bool] = None, predictions: bool = False, cache=None, n_new=None,
+                extend: bool = False, **kwargs):
+        # cache (models/generation.py KVCache): the prefill, one decode step or a chunk of generation; with extend a
+        # forward of any length on the cache (a new turn), of which row b keeps n_new[b] tokens
+        h = self.transformer(input_ids, cache, n_new, extend)
         if predictions:  # evaluation without logits: loss, top-1 token and label rank per position
             return scored_output(self, h, self.lm_head.weight, labels, num_items_in_batch)
         loss = None

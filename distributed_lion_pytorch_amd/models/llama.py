@@ -178,9 +178,9 @@ class LlamaAttention(nn.Module):
             self.q_norm = RMSNorm(self.head_dim, cfg.rms_norm_eps)
             self.k_norm = RMSNorm(self.head_dim, cfg.rms_norm_eps)
 
-    def forward(self, x, cos, sin, bounds=None, cache=None):
+    def forward(self, x, cos, sin, bounds=None, cache=None, extend: bool = False):
         if cache is not None:
-            return self._forward_cached(x, cos, sin, cache)
+            return self._forward_cached(x, cos, sin, cache, extend)
         B, T, _ = x.shape
         q, k, v = _proj(x, (self.q_proj, self.k_proj, self.v_proj))
         q = q.view(B, T, self.n_head, self.head_dim)
@@ -194,24 +194,28 @@ class LlamaAttention(nn.Module):
             y = fused.rope_attention(q, k, v, cos, sin, p, self.window, bounds)
         return _lin(self.o_proj, y)
 
-    def _forward_cached(self, x, cos, sin, cache):
+    def _forward_cached(self, x, cos, sin, cache, extend: bool = False):
         """Generation (models/generation.py KVCache; cos / sin cover the cache's max_len).  Prefill: the prompt's
         rotated k and v are copied into cache[:, :T] and attention is the flash forward.  Decode step (one token
         per row): fused.kv_append rotates q and k at each row's own position and appends k and v, then
-        fused.decode_attention reads the cache once for the whole group of query heads."""
+        fused.decode_attention reads the cache once for the whole group of query heads.  ``extend``: a forward of
+        any T after the prefill, fused.extend_attention above 8 tokens per row."""
         B, T, _ = x.shape
         kc, vc = cache.layer(self.layer_idx)
         ks, vs = cache.layer_scales(self.layer_idx)  # an fp8 cache: kc / vc are codes
         q, k, v = _proj(x, (self.q_proj, self.k_proj, self.v_proj))
         gq, gk, eps = (self.q_norm.weight, self.k_norm.weight, self.q_norm.eps) if hasattr(self, "q_norm") else (None, None, 0.0)
         if cache.prefilled and cache.chunk:
-            # T tokens per row (1 < T <= 8, or ragged): token t at position lengths[b] + t, causal inside the chunk
+            # T tokens per row (1 < T <= 8, any T with extend, or ragged): token t at position lengths[b] + t, causal
+            # inside the chunk
             q = q.view(B, T, self.n_head, self.head_dim)
             k = k.view(B, T, self.n_kv, self.head_dim)
             v = v.view(B, T, self.n_kv, self.head_dim)
             q = fused.kv_append_chunk(q, k, v, cache.lengths, cos, sin, gq, gk, eps, kc, vc, cache.n_new, ks, vs)
             if ks is not None:
                 y = fused.cached_attention_fp8(q, kc, ks, vc, vs, cache.lengths, cache.n_new, self.window, cache.width + T)
+            elif extend:
+                y = fused.extend_attention(q, kc, vc, cache.kv_len, cache.n_new, self.window, cache.width + T)
             else:
                 y = fused.chunk_attention(q, kc, vc, cache.kv_len, cache.n_new, self.window, cache.width + T)
             return _lin(self.o_proj, y)
@@ -330,9 +334,9 @@ class LlamaModel(nn.Module):
                 per_window[w] = fused.visibility_bounds(position_ids, w)
         return [per_window[layer.self_attn.window] for layer in self.layers]
 
-    def forward(self, input_ids, position_ids=None, cache=None, n_new=None):
+    def forward(self, input_ids, position_ids=None, cache=None, n_new=None, extend: bool = False):
         if cache is not None:
-            return self._forward_cached(input_ids, cache, n_new)
+            return self._forward_cached(input_ids, cache, n_new, extend)
         T = input_ids.shape[1]
         x = self.embed_tokens(input_ids)
         # position_ids that restart per document (packed rows) bound every row's
@@ -358,20 +362,20 @@ class LlamaModel(nn.Module):
             x, h = fused.dropout_add_norm(layer.mlp(h), x, nxt.weight, None, nxt.eps, 0.0, rms=True)
         return h
 
-    def _forward_cached(self, input_ids, cache, n_new=None):
+    def _forward_cached(self, input_ids, cache, n_new=None, extend: bool = False):
         """The prefill (first call on a fresh KVCache: the whole prompt), one decode step (one token per row) or
-        a chunk (up to 8 tokens per row, of which row b keeps ``n_new[b]``) of generation: the fused residual +
-        norm chain of ``forward`` with the layers' cached attention."""
+        a chunk (up to 8 tokens per row, any number with ``extend``, of which row b keeps ``n_new[b]``) of
+        generation: the fused residual + norm chain of ``forward`` with the layers' cached attention."""
         B, T = input_ids.shape
-        cache.begin(B, T, n_new)
+        cache.begin(B, T, n_new, extend)
         x = self.embed_tokens(input_ids)
         cos, sin = self.rotary.tables(cache.max_len, x.device, x.dtype)
         first = self.layers[0].input_layernorm
         h = fused.norm(x, first.weight, None, first.eps, rms=True)
         for i, layer in enumerate(self.layers):
             pn = layer.post_attention_layernorm
-            x, h = fused.dropout_add_norm(layer.self_attn(h, cos, sin, None, cache), x, pn.weight, None, pn.eps, 0.0,
-                                          rms=True)
+            x, h = fused.dropout_add_norm(layer.self_attn(h, cos, sin, None, cache, extend), x, pn.weight, None, pn.eps,
+                                          0.0, rms=True)
             nxt = self.layers[i + 1].input_layernorm if i + 1 < len(self.layers) else self.norm
             x, h = fused.dropout_add_norm(layer.mlp(h), x, nxt.weight, None, nxt.eps, 0.0, rms=True)
         cache.advance(T)
@@ -429,11 +433,12 @@ class LlamaForCausalLM(NativeGenerateMixin, LossOptionsMixin, PreTrainedModel):
 
     def forward(self, input_ids=None, labels=None, attention_mask=None, num_items_in_batch=None,
                 return_dict: Optional[bool] = None, position_ids=None, predictions: bool = False, cache=None,
-                **kwargs):
+                n_new=None, extend: bool = False, **kwargs):
         # position_ids is a named parameter: HF's remove_unused_columns keeps only
         # those.  They switch on document-isolated attention (LlamaModel.forward).
-        # cache (models/generation.py KVCache): the prefill or one decode step of generation.
-        h = self.model(input_ids, position_ids, cache)
+        # cache (models/generation.py KVCache): the prefill, one decode step or a chunk of generation; with extend a
+        # forward of any length on the cache (a new turn), of which row b keeps n_new[b] tokens.
+        h = self.model(input_ids, position_ids, cache, n_new, extend)
         if predictions:  # evaluation without logits: loss, top-1 token and label rank per position
             return scored_output(self, h, self.lm_head.weight, labels, num_items_in_batch)
         loss = logits = None

@@ -1394,8 +1394,8 @@ def kv_append_chunk(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pos: torc
     None: all T) to ``cache[b, pos[b] + t]``.  The q rows of the other tokens are computed by the same
     arithmetic and mean nothing.  A written position outside [0, Tmax) is not written and raises through
     check_index_errors (on the CPU: at once).  The rotation and the norm are bit for bit those of ``rope`` /
-    ``qk_norm_rope`` at that position.  bf16 at head_dim 64 / 128 and T <= 8 runs csrc/chunk_attention.hip.
-    ``k_scale`` / ``v_scale``: the fp8 cache, as in ``kv_append``."""
+    ``qk_norm_rope`` at that position.  bf16 at head_dim 64 / 128 runs csrc/chunk_attention.hip for any T.
+    ``k_scale`` / ``v_scale``: the fp8 cache, as in ``kv_append`` (its kernel takes T <= 8, more the PyTorch form)."""
     if (cos is None) != (sin is None) or (q_gamma is None) != (k_gamma is None) or (q_gamma is not None and cos is None):
         raise ValueError("kv_append_chunk: cos / sin and q_gamma / k_gamma come as pairs, gains only with tables")
     if (k_scale is None) != (v_scale is None):
@@ -1413,7 +1413,8 @@ def kv_append_chunk(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pos: torc
                                                  v_scale, _index_flag(q.device))
         return kv_append_chunk_reference(q, k, v, pos, cos, sin, q_gamma, k_gamma, eps, k_cache, v_cache, n_new, k_scale,
                                          v_scale)
-    if (q.dtype == k.dtype == v.dtype == torch.bfloat16 and D in (64, 128) and 1 <= T <= CHUNK_MAX_TOKENS and q.is_cuda
+    if (q.dtype == k.dtype == v.dtype == torch.bfloat16 and D in (64, 128) and T >= 1 and q.is_cuda
+            and q.shape[0] * T * (q.shape[2] + 2 * k.shape[2]) < (1 << 31)
             and pos.is_cuda and pos.dtype == torch.int32 and _cache_ok(k_cache) and _cache_ok(v_cache)
             and (n_new is None or (n_new.is_cuda and n_new.dtype == torch.int32))
             and all(t is None or (t.dtype == torch.bfloat16 and t.shape[0] >= Tmax) for t in (cos, sin))
@@ -1479,6 +1480,59 @@ def chunk_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tenso
         return hip.ops().chunk_attention(q.contiguous(), k_cache, v_cache, kv_len.contiguous(),
                                          None if n_new is None else n_new.contiguous(), window, max_len, s, chunk)
     return chunk_attention_reference(q, k_cache, v_cache, kv_len, n_new, window, max_len)
+
+
+# Any T tokens per sequence against the cache (csrc/extend_attention.hip): a new turn on an existing cache, a prompt
+# prefilled in pieces.
+EXTEND_TQ = 16  # csrc/kernels.h kExtendTQ: the tokens of one block's query tile
+_EXTEND_MAX_SPLITS = _DECODE_MAX_SPLITS  # the partials and the combine pass are chunk_attention's
+_EXTEND_MIN_CHUNK = 256  # keys: four of the kernel's 64-key tiles
+
+
+def extend_splits(B: int, Hkv: int, max_len: int, T: int, window: int = 0, splits=None):
+    """(splits, chunk) of the extend-attention grid: ``splits`` blocks of ``chunk`` keys per (tile of EXTEND_TQ tokens,
+    kv head, row).  A host rule over B, Hkv, max_len (the host bound on kv_len + T), T and the window only.  The keys
+    of a token tile span at most ``max_len``, and ``window + EXTEND_TQ - 1`` under a window; split s owns the keys
+    ``[lo + s chunk, lo + (s + 1) chunk)`` of the tile's range, lo = the window's lower edge of its first token.
+    The count aims at two blocks per CU and falls to 1 as soon as the token tiles fill the grid themselves.
+    ``splits`` forces the count (tests)."""
+    wspan = int(window) + EXTEND_TQ - 1
+    span = wspan if window and wspan < max_len else int(max_len)
+    if splits is None:
+        blocks = max(1, B * Hkv * -(-int(T) // EXTEND_TQ))
+        splits = min(-(-_DECODE_TARGET_BLOCKS // blocks), _EXTEND_MAX_SPLITS, -(-span // _EXTEND_MIN_CHUNK))
+    splits = max(1, min(int(splits), _EXTEND_MAX_SPLITS, span))
+    chunk = -(-span // splits)
+    return -(-span // chunk), chunk
+
+
+extend_attention_reference = chunk_attention_reference  # the PyTorch form has no limit on T
+
+
+def extend_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, kv_len: torch.Tensor, n_new=None,
+                     window: int = 0, max_len=None, splits=None) -> torch.Tensor:
+    """``chunk_attention`` for any T: q [B, T, H, D] (their keys already appended by ``kv_append_chunk``), caches
+    [B, Tmax, Hkv, D], kv_len int32 [B] (the lengths before these tokens) -> [B, T, H * D], with the same meaning of
+    ``n_new``, ``window``, ``max_len`` and ``splits``; ``kv_len = 0`` is causal self-attention read from the cache.
+    T <= 8 is ``chunk_attention``.  Above, bf16 at head_dim 64 / 128 with H / Hkv in 1..8 runs
+    csrc/extend_attention.hip (blocks of 16 tokens x the GQA group, the waves divide the query rows and share 64-key
+    K / V tiles through LDS, tiles above the diagonal or below the window skipped, fp32 partials and
+    chunk_attention's combine pass when the keys are split; no atomics); anything else the PyTorch form."""
+    B, T, H, D = q.shape
+    if T <= CHUNK_MAX_TOKENS:
+        return chunk_attention(q, k_cache, v_cache, kv_len, n_new, window, max_len, splits)
+    Tmax, Hkv = k_cache.shape[1], k_cache.shape[2]
+    window = int(window or 0)
+    max_len = Tmax if max_len is None else max(1, min(int(max_len), Tmax))
+    if (q.dtype == torch.bfloat16 and D in (64, 128) and H % Hkv == 0 and 1 <= H // Hkv <= 8 and q.is_cuda
+            and kv_len.is_cuda and kv_len.dtype == torch.int32
+            and (n_new is None or (n_new.is_cuda and n_new.dtype == torch.int32)) and window < (1 << 30)
+            and _cache_ok(k_cache) and _cache_ok(v_cache) and B <= 65535 and Hkv <= 65535 and B * T * H < (1 << 31)
+            and _use_hip(q)):
+        s, chunk = extend_splits(B, Hkv, max_len, T, window, splits)
+        return hip.ops().extend_attention(q.contiguous(), k_cache, v_cache, kv_len.contiguous(),
+                                          None if n_new is None else n_new.contiguous(), window, max_len, s, chunk)
+    return extend_attention_reference(q, k_cache, v_cache, kv_len, n_new, window, max_len)
 
 
 # ------------------------------------------------- generation on an fp8 (e4m3) KV cache (csrc/kv8.h, kv8_attention.hip)

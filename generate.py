@@ -53,6 +53,8 @@ def parse_args(argv=None):
     ap.add_argument("--num_assistant_tokens", type=int, default=5, help="draft tokens per round (1..7)")
     ap.add_argument("--kv_cache_dtype", default=None, choices=("fp8_e4m3",),
                     help="keep the KV cache as e4m3 codes with one scale per (token, kv head): about half the memory")
+    ap.add_argument("--prefill_chunk_size", type=int, default=None,
+                    help="prefill the prompt in pieces of this many columns (bounds the prefill's activation memory)")
     ap.add_argument("--bf16", action="store_true")
     ap.add_argument("--load_in_4bit", action="store_true",
                     help="keep the base model's linear layers in 4 bits (models/quant.py), as sft_llama2.py does")
@@ -123,7 +125,7 @@ def main(argv=None):
                          num_return_sequences=a.num_return_sequences, length_penalty=a.length_penalty,
                          early_stopping=a.early_stopping, assistant_model=assistant,
                          num_assistant_tokens=a.num_assistant_tokens, return_dict_in_generate=assistant is not None,
-                         kv_cache_dtype=a.kv_cache_dtype)
+                         kv_cache_dtype=a.kv_cache_dtype, prefill_chunk_size=a.prefill_chunk_size)
     sync()
     dt = time.perf_counter() - t0
     spec = None
