@@ -78,6 +78,7 @@ EXTRA_FLAGS = {
     # no packed fp32 arithmetic (v_pk_mul_f32 and kin) in the fp8-cache and extend kernels: plain VALU ops only
     "kv8_attention.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "extend_attention.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "kv8_extend_attention.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

@@ -1737,7 +1737,7 @@ Tensor kv_append_chunk_fp8(const Tensor& q, const Tensor& k, const Tensor& v, co
   TORCH_CHECK(q.dim() == 4, "dlion kv_append_chunk_fp8: q must be [B, T, H, D]");
   const int64_t B = q.size(0), T = q.size(1), H = q.size(2), D = q.size(3);
   TORCH_CHECK(D == 64 || D == 128, "dlion kv_append_chunk_fp8: head_dim must be 64 or 128");
-  TORCH_CHECK(T >= 1 && T <= dlion::kChunkMaxTokens, "dlion kv_append_chunk_fp8: T must be in [1, 8]");
+  TORCH_CHECK(T >= 1 && T < (int64_t{1} << 31), "dlion kv_append_chunk_fp8: T must be >= 1");
   TORCH_CHECK(k.dim() == 4 && v.dim() == 4 && k.size(2) == v.size(2), "dlion kv_append_chunk_fp8: k / v must be [B, T, Hkv, D]");
   const int64_t Hkv = k.size(2);
   check_chunk_rows("kv_append_chunk_fp8", "q", q, B, T, D);
@@ -1811,6 +1811,54 @@ Tensor cached_attention_fp8(const Tensor& q, const Tensor& k_codes, const Tensor
                 static_cast<int>(D), static_cast<int>(Tmax), static_cast<int>(max_len), static_cast<int>(window),
                 static_cast<int>(splits), static_cast<int>(chunk), 1.0f / std::sqrt(static_cast<float>(D)), cur_stream()),
             "cached_attention_fp8");
+  return out;
+}
+
+// cached_attention_fp8 for any T (csrc/kv8_extend_attention.hip); splits / chunk from ops/fused.py extend_splits
+Tensor extend_attention_fp8(const Tensor& q, const Tensor& k_codes, const Tensor& k_scales, const Tensor& v_codes,
+                            const Tensor& v_scales, const Tensor& kv_len, const std::optional<Tensor>& n_new,
+                            int64_t window, int64_t max_len, int64_t splits, int64_t chunk) {
+  TORCH_CHECK(q.dim() == 4 && k_codes.dim() == 4,
+              "dlion extend_attention_fp8: q must be [B, T, H, D], the codes [B, Tmax, Hkv, D]");
+  const int64_t B = q.size(0), T = q.size(1), H = q.size(2), D = q.size(3), Tmax = k_codes.size(1), Hkv = k_codes.size(2);
+  TORCH_CHECK(D == 64 || D == 128, "dlion extend_attention_fp8: head_dim must be 64 or 128");
+  TORCH_CHECK(T >= 1 && T < (int64_t{1} << 31), "dlion extend_attention_fp8: T must be >= 1");
+  TORCH_CHECK(Hkv >= 1 && H % Hkv == 0 && H / Hkv <= 8, "dlion extend_attention_fp8: H / Hkv must be an integer in [1, 8]");
+  TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16 && q.is_contiguous() &&
+                  reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0,
+              "dlion extend_attention_fp8: q must be a contiguous, 16-byte aligned bf16 GPU tensor");
+  check_cache8("extend_attention_fp8", "k", k_codes, k_scales, B, Hkv, D);
+  check_cache8("extend_attention_fp8", "v", v_codes, v_scales, B, Hkv, D);
+  TORCH_CHECK(v_codes.size(1) == Tmax, "dlion extend_attention_fp8: the caches differ in length");
+  TORCH_CHECK(kv_len.is_cuda() && kv_len.scalar_type() == at::kInt && kv_len.is_contiguous() && kv_len.numel() == B,
+              "dlion extend_attention_fp8: kv_len must be a contiguous int32 [B] GPU tensor");
+  const int* nn = chunk_n_new("extend_attention_fp8", n_new, B);
+  TORCH_CHECK(max_len >= 1 && max_len < (int64_t{1} << 31) && window >= 0 && window < (int64_t{1} << 30) &&
+                  splits >= 1 && splits <= dlion::kDecodeMaxSplits && chunk >= 1 && chunk < (int64_t{1} << 31) &&
+                  B <= 65535 && Hkv <= 65535 && B * T * H < (int64_t{1} << 31),
+              "dlion extend_attention_fp8: bad max_len / window / splits / chunk / batch");
+  const c10::DeviceGuard dg(q.device());
+  auto out = at::empty({B, T, H * D}, q.options());
+  Tensor part_ml, part_o;
+  float *pm = nullptr, *pl = nullptr, *po = nullptr;
+  if (splits > 1) {  // one split stores bf16 from the kernel
+    const auto f32 = q.options().dtype(at::kFloat);
+    part_ml = at::empty({2, B, T, H, splits}, f32);
+    part_o = at::empty({B, T, H, splits, D}, f32);
+    pm = part_ml.data_ptr<float>();
+    pl = pm + B * T * H * splits;
+    po = part_o.data_ptr<float>();
+  }
+  check_hip(dlion::launch_extend_attention_fp8(
+                q.data_ptr(), k_codes.data_ptr<uint8_t>(), cache_batch_stride(k_codes), cache_token_stride(k_codes),
+                k_scales.data_ptr<float>(), scale_batch_stride(k_scales), scale_token_stride(k_scales),
+                v_codes.data_ptr<uint8_t>(), cache_batch_stride(v_codes), cache_token_stride(v_codes),
+                v_scales.data_ptr<float>(), scale_batch_stride(v_scales), scale_token_stride(v_scales),
+                kv_len.data_ptr<int>(), nn, pm, pl, po, out.data_ptr(), static_cast<int>(B), static_cast<int>(T),
+                static_cast<int>(H), static_cast<int>(Hkv), static_cast<int>(D), static_cast<int>(Tmax),
+                static_cast<int>(max_len), static_cast<int>(window), static_cast<int>(splits), static_cast<int>(chunk),
+                1.0f / std::sqrt(static_cast<float>(D)), cur_stream()),
+            "extend_attention_fp8");
   return out;
 }
 
@@ -1910,6 +1958,8 @@ TORCH_LIBRARY(dlion, m) {
         " Tensor? q_gamma, Tensor? k_gamma, float eps, Tensor(a!) k_codes, Tensor(b!) v_codes, Tensor(c!) k_scales,"
         " Tensor(d!) v_scales, Tensor(e!) err) -> Tensor");
   m.def("cached_attention_fp8(Tensor q, Tensor k_codes, Tensor k_scales, Tensor v_codes, Tensor v_scales, Tensor kv_len,"
+        " Tensor? n_new, int window, int max_len, int splits, int chunk) -> Tensor");
+  m.def("extend_attention_fp8(Tensor q, Tensor k_codes, Tensor k_scales, Tensor v_codes, Tensor v_scales, Tensor kv_len,"
         " Tensor? n_new, int window, int max_len, int splits, int chunk) -> Tensor");
   m.def("quant4(Tensor w, Tensor code) -> (Tensor, Tensor)");
   m.def("dequant4_(Tensor q, Tensor absmax, Tensor code, Tensor(a!) out) -> ()");
@@ -2056,6 +2106,7 @@ TORCH_LIBRARY_IMPL(dlion, CUDA, m) {
   m.impl("kv_append_fp8", &kv_append_fp8);
   m.impl("kv_append_chunk_fp8", &kv_append_chunk_fp8);
   m.impl("cached_attention_fp8", &cached_attention_fp8);
+  m.impl("extend_attention_fp8", &extend_attention_fp8);
   m.impl("skinny_gemm_nt", &skinny_gemm_nt);
   m.impl("skinny_gemm_w4", &skinny_gemm_w4);
 }

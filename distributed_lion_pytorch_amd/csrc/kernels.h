@@ -267,6 +267,14 @@ hipError_t launch_cached_attention_fp8(const void* q, const uint8_t* k_codes, in
                                        const int* kv_len, const int* n_new, float* part_m, float* part_l,
                                        float* part_o, void* out, int B, int T, int H, int Hkv, int D, int Tmax,
                                        int max_len, int window, int splits, int chunk, float scale, hipStream_t st);
+// launch_extend_attention on the fp8 cache (kv8_extend_attention.hip): any T, the same key ranges, grid, splits
+// and partials; splits == 1 writes out directly (the partials may be null)
+hipError_t launch_extend_attention_fp8(const void* q, const uint8_t* k_codes, int64_t k_bs, int64_t k_ts,
+                                       const float* k_scales, int64_t ks_bs, int64_t ks_ts, const uint8_t* v_codes,
+                                       int64_t v_bs, int64_t v_ts, const float* v_scales, int64_t vs_bs, int64_t vs_ts,
+                                       const int* kv_len, const int* n_new, float* part_m, float* part_l,
+                                       float* part_o, void* out, int B, int T, int H, int Hkv, int D, int Tmax,
+                                       int max_len, int window, int splits, int chunk, float scale, hipStream_t st);
 
 // ---- decode projections (skinny_gemm.hip); bf16, 1 <= M <= 16, K % 64 == 0, any N
 // out[M, N] (row stride ldo) = x[M, K] (row stride ldx, 16-byte aligned rows) . w[N, K]^T (+ bias[N]), fp32

@@ -348,8 +348,8 @@ hipError_t kv_append_chunk_any(const void* q, const void* k, const void* v, int6
                                int64_t vc_ts, float* k_scales, float* v_scales, int64_t sc_bs, int64_t sc_ts, int B,
                                int T, int H, int Hkv, int D, int Tmax, int32_t* err, hipStream_t st) {
   if (B <= 0 || T <= 0 || H <= 0 || Hkv <= 0) return hipSuccess;
-  // the bf16 cache takes any T whose grid fits (extend_attention.hip's forward); the fp8 stores keep the chunk's cap
-  if ((D != 64 && D != 128) || Tmax <= 0 || err == nullptr || (FP8 && T > kChunkMaxTokens)) return hipErrorInvalidValue;
+  // any T whose grid fits, on either cache (the extend kernels' forward)
+  if ((D != 64 && D != 128) || Tmax <= 0 || err == nullptr) return hipErrorInvalidValue;
   if ((cos == nullptr) != (sin == nullptr) || (q_gamma == nullptr) != (k_gamma == nullptr)) return hipErrorInvalidValue;
   if (q_gamma != nullptr && cos == nullptr) return hipErrorInvalidValue;
   const int groups = 256 / (D / 8);

@@ -12,9 +12,10 @@ by ``n_new`` (``fused.kv_append_chunk`` and ``fused.chunk_attention``, csrc/chun
 ``KVCache(..., kv_dtype="fp8_e4m3")`` (``generate(kv_cache_dtype="fp8_e4m3")``) holds e4m3 codes and one power-of-two
 fp32 scale per (token, kv head) instead: (D + 4) / 2D of the bf16 cache's memory.  The prefill quantises the rotated
 k and v with ``fused.kv_quantize`` (the prompt's own attention stays the flash forward on the unquantised k and v),
-a step or a chunk appends through the fp8 stores of ``fused.kv_append`` / ``kv_append_chunk`` and attends through
-``fused.cached_attention_fp8`` (csrc/kv8_attention.hip).  Only the cached keys and values are quantised; the tokens
-may differ from the bf16 cache's.
+a step, a chunk or an ``extend=True`` forward of any length appends through the fp8 stores of ``fused.kv_append`` /
+``kv_append_chunk`` and attends through ``fused.cached_attention_fp8`` (csrc/kv8_attention.hip up to 8 tokens per row,
+csrc/kv8_extend_attention.hip above).  Only the cached keys and values are quantised; the tokens may differ from the
+bf16 cache's.
 
 ``NativeGenerateMixin.generate`` uses HF's argument names: greedy or sampled (temperature, then top-k, then
 top-p), ragged prompts by ``attention_mask`` (left- or right-padded), EOS / pad handling; ``num_beams > 1`` is beam

@@ -1395,7 +1395,7 @@ def kv_append_chunk(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pos: torc
     arithmetic and mean nothing.  A written position outside [0, Tmax) is not written and raises through
     check_index_errors (on the CPU: at once).  The rotation and the norm are bit for bit those of ``rope`` /
     ``qk_norm_rope`` at that position.  bf16 at head_dim 64 / 128 runs csrc/chunk_attention.hip for any T.
-    ``k_scale`` / ``v_scale``: the fp8 cache, as in ``kv_append`` (its kernel takes T <= 8, more the PyTorch form)."""
+    ``k_scale`` / ``v_scale``: the fp8 cache, as in ``kv_append``, for any T as well."""
     if (cos is None) != (sin is None) or (q_gamma is None) != (k_gamma is None) or (q_gamma is not None and cos is None):
         raise ValueError("kv_append_chunk: cos / sin and q_gamma / k_gamma come as pairs, gains only with tables")
     if (k_scale is None) != (v_scale is None):
@@ -1403,7 +1403,8 @@ def kv_append_chunk(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pos: torc
     T, D = q.shape[1], q.shape[-1]
     Tmax = k_cache.shape[1]
     if k_scale is not None:
-        if (1 <= T <= CHUNK_MAX_TOKENS and (n_new is None or (n_new.is_cuda and n_new.dtype == torch.int32))
+        if (T >= 1 and q.shape[0] * T * (q.shape[2] + 2 * k.shape[2]) < (1 << 31)
+                and (n_new is None or (n_new.is_cuda and n_new.dtype == torch.int32))
                 and _append8_ok(q, k, v, pos, cos, sin, q_gamma, k_gamma, k_cache, v_cache, k_scale, v_scale)):
             q, k, v = (t if _chunk_rows_ok(t) else t.contiguous() for t in (q, k, v))
             if cos is not None:
@@ -1617,24 +1618,31 @@ def cached_attention_fp8_reference(q, k_codes, k_scales, v_codes, v_scales, kv_l
 def cached_attention_fp8(q: torch.Tensor, k_codes: torch.Tensor, k_scales: torch.Tensor, v_codes: torch.Tensor,
                          v_scales: torch.Tensor, kv_len: torch.Tensor, n_new=None, window: int = 0, max_len=None,
                          splits=None) -> torch.Tensor:
-    """``chunk_attention`` on an fp8 cache: q [B, T, H, D] (T = 1..8 new queries per row, their keys already appended),
+    """``extend_attention`` on an fp8 cache: q [B, T, H, D] (T new queries per row, any T, their keys already appended),
     codes [B, Tmax, Hkv, D] uint8 and scales [B, Tmax, Hkv] fp32 of k and v, kv_len int32 [B] (the lengths before these
     T tokens) -> [B, T, H * D].  ``n_new`` / ``window`` / ``max_len`` / ``splits`` mean what they mean there; T = 1
     with ``n_new=None`` is the decode step (``decode_attention`` with ``kv_len + 1``).  bf16 q at head_dim 64 / 128
-    with H / Hkv in 1..8 runs csrc/kv8_attention.hip (the chunk kernel's grid, partials and MFMA arithmetic on
-    dequantised operands, the scales folded into the scores and into P; no atomics); anything else the PyTorch form."""
+    with H / Hkv in 1..8 runs HIP: T <= 8 csrc/kv8_attention.hip (the chunk kernel's grid, partials and MFMA arithmetic
+    on dequantised operands), more csrc/kv8_extend_attention.hip (the extend kernel's blocks of 16 tokens x the GQA
+    group under ``extend_splits``, the codes converted to bf16 once per block on their way into LDS); both fold the
+    scales into the scores and into P, exactly, and use no atomics.  Anything else the PyTorch form."""
     B, T, H, D = q.shape
     Tmax, Hkv = k_codes.shape[1], k_codes.shape[2]
     window = int(window or 0)
     max_len = Tmax if max_len is None else max(1, min(int(max_len), Tmax))
-    if (q.dtype == torch.bfloat16 and D in (64, 128) and 1 <= T <= CHUNK_MAX_TOKENS and H % Hkv == 0
+    if (q.dtype == torch.bfloat16 and D in (64, 128) and T >= 1 and H % Hkv == 0
             and 1 <= H // Hkv <= 8 and q.is_cuda and kv_len.is_cuda and kv_len.dtype == torch.int32
             and (n_new is None or (n_new.is_cuda and n_new.dtype == torch.int32)) and window < (1 << 30)
             and _cache8_ok(k_codes, k_scales) and _cache8_ok(v_codes, v_scales) and B <= 65535 and Hkv <= 65535
-            and _use_hip(q)):
+            and (T <= CHUNK_MAX_TOKENS or B * T * H < (1 << 31)) and _use_hip(q)):
+        nn = None if n_new is None else n_new.contiguous()
+        if T > CHUNK_MAX_TOKENS:
+            s, chunk = extend_splits(B, Hkv, max_len, T, window, splits)
+            return hip.ops().extend_attention_fp8(q.contiguous(), k_codes, k_scales, v_codes, v_scales,
+                                                  kv_len.contiguous(), nn, window, max_len, s, chunk)
         s, chunk = chunk_splits(B, Hkv, max_len, T, window, splits)
         return hip.ops().cached_attention_fp8(q.contiguous(), k_codes, k_scales, v_codes, v_scales, kv_len.contiguous(),
-                                              None if n_new is None else n_new.contiguous(), window, max_len, s, chunk)
+                                              nn, window, max_len, s, chunk)
     return cached_attention_fp8_reference(q, k_codes, k_scales, v_codes, v_scales, kv_len, n_new, window, max_len)
 
 
