@@ -304,6 +304,33 @@ std::tuple<Tensor, Tensor, Tensor> lm_topk(const Tensor& logits, int64_t v, int6
   return {values, ids, lse};
 }
 
+// one sampled column per row of read-only logits: (ids, lse, floor, kept), see kernels.h
+std::tuple<Tensor, Tensor, Tensor, Tensor> lm_sample(const Tensor& logits, int64_t v, double inv_t, int64_t top_k,
+                                                     double top_p, int64_t key) {
+  check_dev(logits, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous(), "dlion: logits must be a contiguous [N, Vpad]");
+  TORCH_CHECK(logits.size(1) % 8 == 0 && v > 0 && v <= logits.size(1), "dlion: padded vocab must be a multiple of 8");
+  TORCH_CHECK(logits.size(1) <= (int64_t{1} << 30), "dlion: lm_sample vocabulary too wide");
+  TORCH_CHECK(top_p > 0.0 && top_p <= 1.0, "dlion: lm_sample needs 0 < top_p <= 1, got ", top_p);
+  TORCH_CHECK(top_k >= 0, "dlion: lm_sample needs top_k >= 0, got ", top_k);
+  TORCH_CHECK(static_cast<float>(inv_t) > 0.f && std::isfinite(static_cast<float>(inv_t)),
+              "dlion: lm_sample needs a finite inv_t > 0, got ", inv_t);
+  TORCH_CHECK(key >= 0 && key <= int64_t{0xffffffff}, "dlion: lm_sample key must be a 32-bit value");
+  const c10::DeviceGuard g(logits.device());
+  const int64_t n = logits.size(0);
+  auto ids = at::empty({n}, logits.options().dtype(at::kInt));
+  auto lse = at::empty({n}, logits.options().dtype(at::kFloat));
+  auto floor = at::empty({n}, logits.options().dtype(at::kFloat));
+  auto kept = at::empty({n}, logits.options().dtype(at::kInt));
+  check_hip(dlion::launch_lm_sample(dtype_code(logits.scalar_type()), logits.data_ptr(), n, logits.size(1),
+                                    static_cast<int>(v), static_cast<float>(inv_t),
+                                    static_cast<int>(std::min<int64_t>(top_k, v)), top_p, static_cast<uint32_t>(key),
+                                    ids.data_ptr<int>(), lse.data_ptr<float>(), floor.data_ptr<float>(),
+                                    kept.data_ptr<int>(), cur_stream()),
+            "lm_sample");
+  return {ids, lse, floor, kept};
+}
+
 // ------------------------------------------------------------ flash attention
 void check_bthd(const Tensor& t, const char* name) {
   TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16, "dlion attn: ", name, " must be a bf16 GPU tensor");
@@ -2020,6 +2047,7 @@ TORCH_LIBRARY(dlion, m) {
   m.def("softmax_xent_opts_(Tensor(a!) logits, Tensor labels, int v, float smoothing, float z_loss, int variant=0) -> Tensor");
   m.def("lm_score(Tensor logits, Tensor labels, int v, float smoothing, float z_loss) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("lm_topk(Tensor logits, int v, int k) -> (Tensor, Tensor, Tensor)");
+  m.def("lm_sample(Tensor logits, int v, float inv_t, int top_k, float top_p, int key) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def(
       "lion_local(Tensor meta, int seg_off, int chunk_off, int n_chunks, int dtype, float decay, float neg_lr,"
       " float b1, float omb1, float b2, float omb2, Tensor? gscale=None, int rounding=0, int rkey=0,"
@@ -2052,6 +2080,7 @@ TORCH_LIBRARY_IMPL(dlion, CUDA, m) {
   m.impl("softmax_xent_opts_", &softmax_xent_opts_);
   m.impl("lm_score", &lm_score);
   m.impl("lm_topk", &lm_topk);
+  m.impl("lm_sample", &lm_sample);
   m.impl("attn_fwd", &attn_fwd);
   m.impl("attn_bwd", &attn_bwd);
   m.impl("add_norm_fwd", &add_norm_fwd);

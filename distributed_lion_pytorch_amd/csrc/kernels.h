@@ -182,6 +182,14 @@ hipError_t launch_lm_score(int dt, const void* logits, const int64_t* labels, in
 hipError_t launch_lm_topk(int dt, const void* logits, int64_t n, int64_t vp, int v, int k, float* values, int* ids,
                           float* lse, hipStream_t st);
 
+// ---- LM head sampling, forward only (lm_sample.hip): read-only logits [n, vp], real columns j < v
+// s = fp32(x) * inv_t; top_k in 1..v-1 keeps the columns with fewer than top_k greater s (0 or >= v: off); top_p < 1
+// keeps, among those, the columns with less than top_p of their mass above them; ids [n] = the Gumbel-max draw under
+// the 32-bit key (-1 for a row with no finite column), lse [n] of s, floor [n] = the least surviving s, kept [n] =
+// the number of survivors; one launch, no float atomics, bit-equal on equal inputs
+hipError_t launch_lm_sample(int dt, const void* logits, int64_t n, int64_t vp, int v, float inv_t, int top_k,
+                            double top_p, uint32_t key, int* ids, float* lse, float* floor, int* kept, hipStream_t st);
+
 // ---- generation (decode.hip); bf16, D in {64, 128}
 // One decode step's q [B, H, D] / k / v [B, Hkv, D] (row strides *_ld, heads contiguous): q and k normed (gains
 // nullable, Qwen3) and rotated (tables [>= Tmax, D], nullable) at pos[b], clamped into [0, Tmax) with

@@ -26,6 +26,7 @@ bounds the key range), graph capture, speculative sampling.
 """
 from __future__ import annotations
 
+import random
 from typing import NamedTuple, Optional
 
 import torch
@@ -251,7 +252,7 @@ class NativeGenerateMixin:
                  seed: Optional[int] = None, num_beams: int = 1, num_return_sequences: int = 1,
                  length_penalty: float = 1.0, early_stopping: bool = False, return_dict_in_generate: bool = False,
                  assistant_model=None, num_assistant_tokens: int = 5, kv_cache_dtype: Optional[str] = None,
-                 prefill_chunk_size: Optional[int] = None):
+                 prefill_chunk_size: Optional[int] = None, sampler: str = "torch"):
         """[B, T0] prompts -> [B, T0 + n_new] long: the prompt exactly as given, then the new tokens.
 
         Greedy takes the top-1 of ``fused.lm_head_score`` (the lowest id on ties, no [B, V] tensor); sampling
@@ -286,7 +287,18 @@ class NativeGenerateMixin:
         columns: the flash forward of the first N columns, then forwards of N columns each on the cache
         (``extend=True``: ``fused.kv_append_chunk`` and ``fused.extend_attention``), ragged prompts by ``n_new``; every
         row's last hidden state is taken from the piece it falls in.  It applies to greedy decoding, sampling, beam
-        search and the target of ``assistant_model``.  Default None: one prefill of the whole prompt."""
+        search and the target of ``assistant_model``.  Default None: one prefill of the whole prompt.
+
+        ``sampler="fused"`` (with ``do_sample=True``) takes step i's tokens from ``fused.lm_head_sample(h, weight,
+        temperature, top_k, top_p, seed, step=i)``: the head GEMM and one kernel launch (csrc/lm_sample.hip), no
+        [B, V] fp32 tensor and no ``torch.Generator``.  The draw is Gumbel-max on a hash of (seed, step, row, token),
+        so a seed gives other tokens than it gives under ``"torch"`` (the default: the warp / softmax / multinomial
+        chain), and top-p keeps or drops equal logits together; ``seed=None`` takes one random seed per call."""
+        if sampler not in ("torch", "fused"):
+            raise ValueError(f"generate: sampler must be 'torch' or 'fused', got {sampler!r}")
+        if sampler == "fused" and (not do_sample or num_beams != 1 or assistant_model is not None):
+            raise ValueError("generate: sampler='fused' is the sampling kernel; it needs do_sample=True, num_beams=1 "
+                             "and no assistant_model")
         if prefill_chunk_size is not None:
             prefill_chunk_size = int(prefill_chunk_size)
             if prefill_chunk_size < 1:
@@ -360,7 +372,9 @@ class NativeGenerateMixin:
             return out if return_dict_in_generate else out.sequences
         cache = KVCache(cfg, B, total, dev, weight.dtype, kv_cache_dtype)
         gen = None
-        if do_sample and seed is not None:
+        if sampler == "fused":
+            draw_seed = int(seed) if seed is not None else random.getrandbits(63)
+        elif do_sample and seed is not None:
             gen = torch.Generator(device=dev)
             gen.manual_seed(int(seed))
 
@@ -371,7 +385,9 @@ class NativeGenerateMixin:
         done_at = torch.full((B,), max_new_tokens, dtype=torch.long, device=dev)  # the step a row emitted EOS at
         ignore = torch.full((B,), -100, dtype=torch.long, device=dev)
         for i in range(max_new_tokens):
-            if do_sample:
+            if sampler == "fused":
+                tok = fused.lm_head_sample(h, weight, temperature, top_k, top_p, draw_seed, step=i).ids.long()
+            elif do_sample:
                 logits = warp_logits(gemm_fwd(h, weight), temperature, top_k, top_p)
                 tok = torch.multinomial(logits.softmax(-1), 1, generator=gen)[:, 0]
             else:

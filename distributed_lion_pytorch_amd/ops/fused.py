@@ -2435,6 +2435,108 @@ def lm_head_topk(h: torch.Tensor, weight: torch.Tensor, k: int) -> LMTopK:
         return LMTopK(values, ids, lse)
 
 
+# --------------------------------------------- LM head sampling (forward only)
+class LMSample(NamedTuple):
+    """What :func:`lm_head_sample` returns per row of the head's logits: the drawn token
+    ``ids`` [N] (int32, -1 for a row with no finite logit), the logsumexp ``lse`` [N] of
+    the logits over the temperature (fp32), the smallest surviving scaled logit ``floor``
+    [N] (fp32) and the number of surviving tokens ``kept`` [N] (int32)."""
+
+    ids: torch.Tensor
+    lse: torch.Tensor
+    floor: torch.Tensor
+    kept: torch.Tensor
+
+
+def sample_gumbel(cols: torch.Tensor, rows: torch.Tensor, key: int, dtype=torch.float32) -> torch.Tensor:
+    """The Gumbel noise of csrc/lm_sample.hip for int64 ``cols`` / ``rows`` (broadcast) under the 32-bit ``key``:
+    n = mix32(mix32(col ^ key) + row * 0x9E3779B1 + 0x85EBCA6B) >> 8, u = (n + 0.5) 2^-24, g = -log(-log(u)).
+    From n = 2^23 on, -log(u) is taken as -log1p(-(2^24 - n - 0.5) 2^-24): n + 0.5 is not an fp32 number there,
+    1 - u is."""
+    from .reference import _M32, _mix32
+
+    h = _mix32((_mix32((cols ^ int(key)) & _M32) + rows * 0x9E3779B1 + 0x85EBCA6B) & _M32)
+    n = h >> 8
+    lo = (n.to(dtype) + 0.5) * 2.0 ** -24
+    hi = ((2 ** 24 - n).to(dtype) - 0.5) * 2.0 ** -24
+    e = torch.where(n < 2 ** 23, -torch.log(lo), -torch.log1p(-hi))
+    return -torch.log(e)
+
+
+def _lm_sample_torch(logits: torch.Tensor, v: int, inv_t: float, top_k: int, top_p: float, key: int):
+    """PyTorch form of the sampling kernel (csrc/lm_sample.hip) on logits [N, Vp], real
+    columns j < v, in fp32: (ids int32, lse fp32, floor fp32, kept int32).  s = fp32(x) *
+    fp32(inv_t); NaN and -inf columns are never kept; ``top_k`` in 1..v-1 keeps the
+    columns with fewer than top_k greater values; ``top_p < 1`` keeps, among those, the
+    columns with less than top_p of their mass above them (equal values together, the
+    maximum always); the token is the argmax of s + g over them (:func:`sample_gumbel`)."""
+    if not 0.0 < top_p <= 1.0 or top_k < 0 or not inv_t > 0:
+        raise ValueError(f"dlion: lm_sample needs 0 < top_p <= 1, top_k >= 0, inv_t > 0; got {top_p}, {top_k}, {inv_t}")
+    n = logits.shape[0]
+    dev = logits.device
+    s = logits[:, :v].float() * torch.tensor(inv_t, dtype=torch.float32, device=dev)
+    s = torch.where(torch.isnan(s), torch.full_like(s, float("-inf")), s)
+    lse = torch.logsumexp(s, dim=1)
+    keep = s > float("-inf")
+    if 1 <= top_k < v:
+        keep &= s >= torch.topk(s, int(top_k), dim=1).values[:, -1:]
+    if top_p < 1.0:
+        srt, order = torch.sort(torch.where(keep, s, torch.full_like(s, float("-inf"))), dim=1, descending=True)
+        p = srt.double().softmax(-1)
+        above = p.cumsum(-1) - p  # mass before each column; equal values take their first column's
+        first = torch.searchsorted(-srt, -srt, right=False)
+        drop = above.gather(1, first) >= top_p
+        drop[:, 0] = False
+        keep &= ~torch.zeros_like(drop).scatter(1, order, drop)
+    cols = torch.arange(v, device=dev)[None, :]
+    rows = torch.arange(n, device=dev)[:, None]
+    score = torch.where(keep, s + sample_gumbel(cols, rows, key), torch.full_like(s, float("-inf")))
+    any_kept = keep.any(dim=1)
+    first_best = torch.where(score == score.max(dim=1, keepdim=True).values, cols, cols.new_full((), v)).min(dim=1).values
+    ids = torch.where(any_kept, first_best, torch.full_like(first_best, -1)).to(torch.int32)
+    floor = torch.where(keep, s, torch.full_like(s, float("inf"))).min(dim=1).values
+    return ids, lse, floor, keep.sum(dim=1).to(torch.int32)
+
+
+def lm_head_sample(h: torch.Tensor, weight: torch.Tensor, temperature: float = 1.0, top_k: int = 0,
+                   top_p: float = 1.0, seed: int = 0, step: int = 0) -> LMSample:
+    """One token per row drawn from the LM head ``h @ weight.T`` after temperature, top-k
+    and top-p (in that order, as ``generate``), without keeping logits: one GEMM into a
+    transient [N, Vp] block and one read-only kernel launch over it (csrc/lm_sample.hip).
+    The draw is Gumbel-max on a counter-based hash of (``seed``, ``step``, row, token):
+    the same arguments give the same tokens, on any batch split that keeps the row
+    numbers.  Top-p treats equal logits as one class (kept or dropped together).
+    Forward only, as :func:`lm_head_score`."""
+    if torch.is_grad_enabled() and (h.requires_grad or weight.requires_grad):
+        raise RuntimeError("dlion: lm_head_sample is forward-only (no gradient reaches h or the weight); "
+                           "call it under torch.no_grad()")
+    temperature, top_k, top_p = float(temperature), int(top_k), float(top_p)
+    if not temperature > 0 or not 0.0 < top_p <= 1.0 or top_k < 0:
+        raise ValueError(f"dlion: lm_head_sample needs temperature > 0, 0 < top_p <= 1 and top_k >= 0, got "
+                         f"{temperature}, {top_p}, {top_k}")
+    from .reference import sr_key
+
+    key = sr_key(seed, step)
+    inv_t = torch.tensor(1.0 / temperature, dtype=torch.float32).item()
+    with torch.no_grad():
+        h2d = h.reshape(-1, h.shape[-1])
+        v = weight.shape[0]
+        if h2d.is_cuda:
+            from .linear import autocast_inputs
+
+            h2d, weight = autocast_inputs(h2d, weight)
+        elif h2d.dtype != weight.dtype:
+            h2d = h2d.to(weight.dtype)
+        with torch.autocast("cuda", enabled=False) if h2d.is_cuda else contextlib.nullcontext():
+            logits = gemm_fwd(h2d, _pad_rows(weight))  # [N, Vp] in the compute dtype, read-only below
+            if logits.dtype in _SCORE_DTYPES and _use_hip(logits):
+                out = hip.ops().lm_sample(logits.contiguous(), v, inv_t, top_k, top_p, key)
+            else:
+                out = _lm_sample_torch(logits, v, inv_t, top_k, top_p, key)
+            del logits
+        return LMSample(*out)
+
+
 def token_predictions(logits, labels=None):
     """``preprocess_logits_for_metrics`` of the package: the (predictions,
     label_ranks) pair of a scored evaluation step passes through; full logits

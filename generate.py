@@ -44,6 +44,8 @@ def parse_args(argv=None):
     ap.add_argument("--top_k", type=int, default=0)
     ap.add_argument("--top_p", type=float, default=1.0)
     ap.add_argument("--seed", type=int, default=None)
+    ap.add_argument("--sampler", choices=["torch", "fused"], default="torch",
+                    help="with --do_sample: 'fused' draws with the LM-head sampling kernel (fused.lm_head_sample)")
     ap.add_argument("--num_beams", type=int, default=1, help="beam search (greedy only; HF's semantics)")
     ap.add_argument("--num_return_sequences", type=int, default=1, help="beams returned per prompt, best first")
     ap.add_argument("--length_penalty", type=float, default=1.0)
@@ -125,7 +127,8 @@ def main(argv=None):
                          num_return_sequences=a.num_return_sequences, length_penalty=a.length_penalty,
                          early_stopping=a.early_stopping, assistant_model=assistant,
                          num_assistant_tokens=a.num_assistant_tokens, return_dict_in_generate=assistant is not None,
-                         kv_cache_dtype=a.kv_cache_dtype, prefill_chunk_size=a.prefill_chunk_size)
+                         kv_cache_dtype=a.kv_cache_dtype, prefill_chunk_size=a.prefill_chunk_size,
+                         sampler=a.sampler)
     sync()
     dt = time.perf_counter() - t0
     spec = None

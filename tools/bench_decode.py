@@ -3,7 +3,7 @@
 math SDPA path, the skinny-M weight GEMMs (bf16 and 4-bit) against the same copy rate and against the general
 dispatch, and end-to-end ``generate`` against the naive recompute loop, with a per-phase split of a decode
 step; the LM-head top-k kernel against the PyTorch chain and beam search end to end (``--topk``,
-``--num_beams``).  Writes a text report (default profiles/r13/decode.txt).
+``--num_beams``); the LM-head sampling kernel against the warp / multinomial chain (``--sample``).  Writes a text report (default profiles/r13/decode.txt).
 
     python tools/bench_decode.py                      # everything
     python tools/bench_decode.py --skip_e2e           # the kernel tables only
@@ -11,6 +11,7 @@ step; the LM-head top-k kernel against the PyTorch chain and beam search end to 
     python tools/bench_decode.py --skip_kernel --skip_skinny --e2e llama3-4bit --ab   # skinny GEMM on / off, interleaved
     python tools/bench_decode.py --skip_kernel --skip_skinny --topk --num_beams 4 --e2e gpt2 --e2e llama3 \
         --out profiles/r14/beam.txt                   # the top-k kernel table and beam search next to greedy
+    python tools/bench_decode.py --skip_kernel --skip_skinny --skip_e2e --sample --out profiles/lm_sample.txt
 
 Method.  Kernel times are device events around ``iters`` back-to-back calls after a warm-up, the calls rotating
 over enough distinct cache buffers that the working set exceeds the 256 MiB Infinity Cache (a decode step of a
@@ -241,6 +242,89 @@ def topk_table(dev, iters):
     return lines
 
 
+# ------------------------------------------------------------------------------------------ LM-head sampling
+SAMPLE_HEADS = [("gpt2", 50257, 768), ("llama-3-8b", 128256, 4096)]
+SAMPLE_ROWS = (1, 8, 16)
+SAMPLE_KW = dict(temperature=0.8, top_k=50, top_p=0.95)
+
+
+def sample_table(dev, iters):
+    """csrc/lm_sample.hip against the chain generate(sampler="torch") runs on the same bf16 logits (warp_logits,
+    softmax, multinomial), and fused.lm_head_sample against the head GEMM + that chain.  Device time is the summed
+    kernel durations of a profiler trace per call (_device_time), wall time is device events around back-to-back
+    calls (_time): the chain is a dozen short launches, so its wall time is what a decode step pays.  The logits
+    are 2 * randn in bf16 and rotate over 4 buffers that stay inside the L2 / Infinity Cache, as after the GEMM."""
+    from distributed_lion_pytorch_amd.models.generation import warp_logits
+    from distributed_lion_pytorch_amd.ops.reference import sr_key
+
+    t, k, p = SAMPLE_KW["temperature"], SAMPLE_KW["top_k"], SAMPLE_KW["top_p"]
+    inv_t = torch.tensor(1.0 / t, dtype=torch.float32).item()
+    lines = [f"{'head':>10s} {'V':>6s} {'N':>2s} | {'kernel us':>9s} {'chain us':>8s} {'chain/kernel':>12s} | {'kernel wall us':>14s} "
+             f"{'chain wall us':>13s} {'ratio':>6s} | {'GEMM+kernel wall us':>19s} {'GEMM+chain wall us':>18s} {'ratio':>6s} | kept"]
+    g = torch.Generator(device=dev).manual_seed(0)
+    gen = torch.Generator(device=dev).manual_seed(1)
+    for name, V, C in SAMPLE_HEADS:
+        # a Parameter, as a model's head: its padded copy is cached instead of rebuilt per call
+        w = torch.nn.Parameter((torch.randn(V, C, device=dev, generator=g) * 0.02).bfloat16(), requires_grad=False)
+        for N in SAMPLE_ROWS:
+            vp = (V + 63) // 64 * 64
+            xs = [(2 * torch.randn(N, vp, device=dev, generator=g)).bfloat16() for _ in range(4)]
+            hs = [torch.randn(N, C, device=dev, generator=g).bfloat16() for _ in range(4)]
+
+            def kernel(i):
+                return hip.ops().lm_sample(xs[i], V, inv_t, k, p, sr_key(0, i))
+
+            def chain(i, logits=None):
+                x = xs[i][:, :V] if logits is None else logits
+                return torch.multinomial(warp_logits(x, t, k, p).softmax(-1), 1, generator=gen)[:, 0]
+
+            with torch.no_grad():
+                d_k, d_c = _device_time(kernel, 4, iters), _device_time(chain, 4, iters)
+                w_k, w_c = _time(kernel, 4, iters), _time(chain, 4, iters)
+                o_k = _time(lambda i: fused.lm_head_sample(hs[i], w, seed=0, step=i, **SAMPLE_KW), 4, iters)
+                o_c = _time(lambda i: chain(i, linear.gemm_fwd(hs[i], w)), 4, iters)
+            kept = hip.ops().lm_sample(xs[0], V, inv_t, k, p, 0)[3].tolist()
+            row = (f"{name:>10s} {V:6d} {N:2d} | {d_k * 1e6:9.1f} {d_c * 1e6:8.1f} {d_c / d_k:11.2f}x | {w_k * 1e6:14.1f} "
+                   f"{w_c * 1e6:13.1f} {w_c / w_k:5.2f}x | {o_k * 1e6:19.1f} {o_c * 1e6:18.1f} {o_c / o_k:5.2f}x | "
+                   f"{min(kept)}..{max(kept)}")
+            lines.append(row)
+            print(row, flush=True)
+            del xs, hs
+        del w
+        torch.cuda.empty_cache()
+    return lines
+
+
+def sample_end_to_end(model_name, dev, prompt=128, new=64):
+    """A generate decode step with each sampler at B in SAMPLE_ROWS: (wall(new tokens) - wall(1 token)) / (new - 1),
+    the two samplers alternating over two rounds, the better round of each reported."""
+    cfg = load_config(model_name)
+    torch.manual_seed(0)
+    with torch.device(dev):
+        model = build_model(cfg, native=True).to(dtype=torch.bfloat16)
+    model.eval()
+    lines = [f"{model_name}: {prompt} prompt + {new} new tokens, bf16, random weights, do_sample=True {SAMPLE_KW}"]
+    for B in SAMPLE_ROWS:
+        ids = torch.randint(0, cfg.vocab_size, (B, prompt), device=dev)
+        per = {"torch": [], "fused": []}
+        for sampler in per:
+            model.generate(ids, max_new_tokens=4, do_sample=True, seed=0, sampler=sampler, **SAMPLE_KW)  # warm-up
+        for _ in range(2):
+            for sampler in per:
+                def call(n):
+                    return model.generate(ids, max_new_tokens=n, do_sample=True, seed=0, sampler=sampler, **SAMPLE_KW)
+                tn, _ = _wall(lambda: call(new))
+                t1, _ = _wall(lambda: call(1))
+                per[sampler].append((tn - t1) / (new - 1) * 1e3)
+        a, b = min(per["torch"]), min(per["fused"])
+        lines.append(f"  B = {B:2d}: ms per decode step  torch {a:.3f} (rounds {per['torch'][0]:.3f} {per['torch'][1]:.3f})  "
+                     f"fused {b:.3f} (rounds {per['fused'][0]:.3f} {per['fused'][1]:.3f})  fused / torch {b / a:.3f}")
+        print(lines[-1], flush=True)
+    del model
+    torch.cuda.empty_cache()
+    return lines
+
+
 # ------------------------------------------------------------------------------------------ end to end
 E2E = {"gpt2": dict(model="gpt2", B=8, prompt=128, new=256), "llama3": dict(model="llama-3-8b", B=8, prompt=512, new=256),
        "llama3-b1": dict(model="llama-3-8b", B=1, prompt=512, new=256),
@@ -461,6 +545,9 @@ def main(argv=None):
     ap.add_argument("--e2e", action="append", choices=sorted(E2E), default=None)
     ap.add_argument("--naive_steps", type=int, default=16)
     ap.add_argument("--topk", action="store_true", help="the LM-head top-k kernel table (csrc/lm_topk.hip)")
+    ap.add_argument("--sample", action="store_true",
+                    help="the LM-head sampling kernel (csrc/lm_sample.hip) and fused.lm_head_sample against the warp_logits "
+                         "+ multinomial chain, and a generate decode step with each sampler, on GPT-2 and Llama-3-8B")
     ap.add_argument("--num_beams", type=int, default=1,
                     help="end to end: beam search at B / num_beams prompts next to greedy at B rows, instead of the "
                          "generate / naive-loop / phase report")
@@ -493,6 +580,13 @@ def main(argv=None):
                 "time = summed kernel durations of a profiler trace", ""]
         print("\n".join(head), flush=True)
         report += head + topk_table(dev, a.iters) + [""]
+    if a.sample:
+        head = ["## LM-head sampling (csrc/lm_sample.hip) against warp_logits + softmax + multinomial on the same bf16 "
+                f"logits, {SAMPLE_KW}; device time = summed kernel durations of a profiler trace, wall = back-to-back calls", ""]
+        print("\n".join(head), flush=True)
+        report += head + sample_table(dev, a.iters) + ["", "## generate decode step by sampler", ""]
+        for name, _, _ in SAMPLE_HEADS:
+            report += sample_end_to_end(name, dev) + [""]
     if not a.skip_e2e:
         report += ["## end to end", ""]
         for name in a.e2e or sorted(E2E):
