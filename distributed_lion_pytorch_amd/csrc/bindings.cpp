@@ -331,6 +331,54 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> lm_sample(const Tensor& logits, int64
   return {ids, lse, floor, kept};
 }
 
+// speculative sampling's verify step: (accepted, next, flags, resid, px, qx), see kernels.h
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> spec_verify(
+    const Tensor& t_logits, const Tensor& d_logits, const Tensor& drafts, const Tensor& t_floor, const Tensor& d_floor,
+    const Tensor& bonus, int64_t v, double inv_t, int64_t key, Tensor arrive) {
+  check_dev(t_logits, "t_logits");
+  check_dev(d_logits, "d_logits");
+  TORCH_CHECK(t_logits.dim() == 3 && t_logits.is_contiguous() && d_logits.dim() == 3 && d_logits.is_contiguous(),
+              "dlion: spec_verify logits must be contiguous [B, kk + 1, Vpad] and [B, kk, Vpad]");
+  TORCH_CHECK(t_logits.scalar_type() == d_logits.scalar_type() && t_logits.device() == d_logits.device(),
+              "dlion: spec_verify needs both logit blocks in one dtype on one device");
+  const int64_t B = d_logits.size(0), kk = d_logits.size(1), vp = d_logits.size(2);
+  TORCH_CHECK(kk >= 1 && kk <= 7, "dlion: spec_verify needs 1 <= kk <= 7 drafts per row, got ", kk);
+  TORCH_CHECK(t_logits.size(0) == B && t_logits.size(1) == kk + 1 && t_logits.size(2) == vp,
+              "dlion: spec_verify t_logits must be [B, kk + 1, Vpad] beside d_logits [B, kk, Vpad]");
+  TORCH_CHECK(vp % 8 == 0 && v > 0 && v <= vp, "dlion: padded vocab must be a multiple of 8");
+  TORCH_CHECK(vp <= (int64_t{1} << 30), "dlion: spec_verify vocabulary too wide");
+  TORCH_CHECK(B <= 65535, "dlion: spec_verify takes at most 65535 batch rows, got ", B);
+  TORCH_CHECK(static_cast<float>(inv_t) > 0.f && std::isfinite(static_cast<float>(inv_t)),
+              "dlion: spec_verify needs a finite inv_t > 0, got ", inv_t);
+  TORCH_CHECK(key >= 0 && key <= int64_t{0xffffffff}, "dlion: spec_verify key must be a 32-bit value");
+  auto check_vec = [&](const Tensor& t, at::ScalarType ty, std::initializer_list<int64_t> shape, const char* name) {
+    TORCH_CHECK(t.device() == d_logits.device() && t.scalar_type() == ty && t.is_contiguous() &&
+                    t.sizes() == at::IntArrayRef(shape),
+                "dlion: spec_verify ", name, " has the wrong device, dtype, shape or strides");
+  };
+  check_vec(drafts, at::kInt, {B, kk}, "drafts [B, kk] int32");
+  check_vec(t_floor, at::kFloat, {B, kk + 1}, "t_floor [B, kk + 1] fp32");
+  check_vec(d_floor, at::kFloat, {B, kk}, "d_floor [B, kk] fp32");
+  check_vec(bonus, at::kInt, {B}, "bonus [B] int32");
+  TORCH_CHECK(arrive.device() == d_logits.device() && arrive.scalar_type() == at::kInt && arrive.is_contiguous() &&
+                  arrive.dim() == 1 && arrive.size(0) >= B,
+              "dlion: spec_verify arrive must be a zeroed int32 workspace of at least B elements");
+  const c10::DeviceGuard g(d_logits.device());
+  const auto ints = d_logits.options().dtype(at::kInt), floats = d_logits.options().dtype(at::kFloat);
+  auto accepted = at::empty({B}, ints), next = at::empty({B}, ints);
+  auto flags = at::empty({B, kk}, ints), resid = at::empty({B, kk}, ints);
+  auto px = at::empty({B, kk}, floats), qx = at::empty({B, kk}, floats);
+  check_hip(dlion::launch_spec_verify(dtype_code(d_logits.scalar_type()), t_logits.data_ptr(), d_logits.data_ptr(),
+                                      drafts.data_ptr<int>(), t_floor.data_ptr<float>(), d_floor.data_ptr<float>(),
+                                      bonus.data_ptr<int>(), B, static_cast<int>(kk), vp, static_cast<int>(v),
+                                      static_cast<float>(inv_t), static_cast<uint32_t>(key), arrive.data_ptr<int>(),
+                                      flags.data_ptr<int>(), resid.data_ptr<int>(), px.data_ptr<float>(),
+                                      qx.data_ptr<float>(), accepted.data_ptr<int>(), next.data_ptr<int>(),
+                                      cur_stream()),
+            "spec_verify");
+  return {accepted, next, flags, resid, px, qx};
+}
+
 // ------------------------------------------------------------ flash attention
 void check_bthd(const Tensor& t, const char* name) {
   TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16, "dlion attn: ", name, " must be a bf16 GPU tensor");
@@ -2048,6 +2096,8 @@ TORCH_LIBRARY(dlion, m) {
   m.def("lm_score(Tensor logits, Tensor labels, int v, float smoothing, float z_loss) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("lm_topk(Tensor logits, int v, int k) -> (Tensor, Tensor, Tensor)");
   m.def("lm_sample(Tensor logits, int v, float inv_t, int top_k, float top_p, int key) -> (Tensor, Tensor, Tensor, Tensor)");
+  m.def("spec_verify(Tensor t_logits, Tensor d_logits, Tensor drafts, Tensor t_floor, Tensor d_floor, Tensor bonus,"
+        " int v, float inv_t, int key, Tensor(a!) arrive) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
   m.def(
       "lion_local(Tensor meta, int seg_off, int chunk_off, int n_chunks, int dtype, float decay, float neg_lr,"
       " float b1, float omb1, float b2, float omb2, Tensor? gscale=None, int rounding=0, int rkey=0,"
@@ -2081,6 +2131,7 @@ TORCH_LIBRARY_IMPL(dlion, CUDA, m) {
   m.impl("lm_score", &lm_score);
   m.impl("lm_topk", &lm_topk);
   m.impl("lm_sample", &lm_sample);
+  m.impl("spec_verify", &spec_verify);
   m.impl("attn_fwd", &attn_fwd);
   m.impl("attn_bwd", &attn_bwd);
   m.impl("add_norm_fwd", &add_norm_fwd);

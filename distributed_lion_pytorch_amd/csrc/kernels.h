@@ -190,6 +190,19 @@ hipError_t launch_lm_topk(int dt, const void* logits, int64_t n, int64_t vp, int
 hipError_t launch_lm_sample(int dt, const void* logits, int64_t n, int64_t vp, int v, float inv_t, int top_k,
                             double top_p, uint32_t key, int* ids, float* lse, float* floor, int* kept, hipStream_t st);
 
+// ---- speculative sampling's verify step, forward only (spec_verify.hip): read-only t_logits [batch, kk + 1, vp] and
+// d_logits [batch, kk, vp] of one dtype, real columns j < v, 1 <= kk <= 7, batch <= 65535; drafts [batch, kk], the
+// floors lm_sample left on the target rows [batch, kk + 1] and the draft rows [batch, kk], bonus [batch] = the draw on
+// target row (b, kk).  Per verify row r = b kk + i: p and q are the softmaxes of s = fp32(x) * inv_t over the finite
+// columns at or above the row's floor; flags = 1 iff 0 <= x < v and u q_x < p_x, u the row's uniform under the key;
+// resid = the Gumbel-max draw from max(0, p - q) where flags == 0, else -1; px, qx = p_x, q_x.  accepted [batch] =
+// the leading ones of a row's flags, next [batch] = bonus if all kk, else the resid after them.  arrive [batch] is an
+// int32 workspace that is zero before the launch and zero after it; one launch, no float atomics
+hipError_t launch_spec_verify(int dt, const void* t_logits, const void* d_logits, const int* drafts,
+                              const float* t_floor, const float* d_floor, const int* bonus, int64_t batch, int kk,
+                              int64_t vp, int v, float inv_t, uint32_t key, int* arrive, int* flags, int* resid,
+                              float* px, float* qx, int* accepted, int* next, hipStream_t st);
+
 // ---- generation (decode.hip); bf16, D in {64, 128}
 // One decode step's q [B, H, D] / k / v [B, Hkv, D] (row strides *_ld, heads contiguous): q and k normed (gains
 // nullable, Qwen3) and rotated (tables [>= Tmax, D], nullable) at pos[b], clamped into [0, Tmax) with

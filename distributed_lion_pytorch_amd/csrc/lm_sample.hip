@@ -25,7 +25,7 @@
 //            Digits that the storage type cannot set (bf16 and fp16 rows at temperature 1) are skipped.
 //   draw     Gumbel scores for the survivors only, (score, column) reduced by max / lowest column; the same sweep
 //            counts the survivors and takes their minimum.
-#include "common.h"
+#include "sampling.h"
 
 #include <climits>
 
@@ -49,18 +49,6 @@ __device__ __forceinline__ uint32_t samp_key(float f) {  // monotone in f, -0.0 
 // 32.32 fixed-point exp(s - m), s <= m; expf is the accurate one (the same s gives the same q in every pass)
 __device__ __forceinline__ unsigned long long samp_mass(float s, float m) {
   return static_cast<unsigned long long>(expf(s - m) * 4294967296.f);
-}
-
-// g = -log(-log(u)), u = (n + 0.5) 2^-24 with n the hash's top 24 bits.  n + 0.5 has 25 significant bits from
-// n = 2^23 on, so the upper half goes through 1 - u = (2^24 - n - 0.5) 2^-24, which is exact there, and log1p.
-__device__ __forceinline__ float samp_gumbel(uint32_t col, uint32_t key, uint32_t rowterm) {
-  const uint32_t n = mix32(mix32(col ^ key) + rowterm) >> 8;
-  float e;
-  if (n < (1u << 23))
-    e = -logf((static_cast<float>(n) + 0.5f) * 0x1p-24f);
-  else
-    e = -log1pf(-((static_cast<float>((1u << 24) - n) - 0.5f) * 0x1p-24f));
-  return -logf(e);
 }
 
 template <int DT>
@@ -287,7 +275,7 @@ lm_sample_kernel(const typename Elem<DT>::S* __restrict__ logits, int64_t vp, in
   }
 
   // ---- draw among the survivors
-  const uint32_t rowterm = static_cast<uint32_t>(row) * 0x9E3779B1u + 0x85EBCA6Bu;
+  const uint32_t rowterm = samp_rowterm(static_cast<uint32_t>(row));
   float best = -INFINITY, least = INFINITY;
   int best_c = INT_MAX, cnt = 0;
   for_each([&](float s, int col) {

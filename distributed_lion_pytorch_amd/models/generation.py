@@ -22,10 +22,13 @@ top-p), ragged prompts by ``attention_mask`` (left- or right-padded), EOS / pad 
 search (HF's semantics) on ``fused.lm_head_topk``; ``assistant_model`` is greedy speculative decoding (a draft
 model proposes, one chunk forward of this model checks).  Out of scope: beam sampling, diverse / constrained
 beams, repetition penalties, a paged or rolling cache (a windowed layer keeps its full-length cache and only
-bounds the key range), graph capture, speculative sampling.
+bounds the key range), graph capture.  ``sampler="speculative"`` with ``do_sample=True`` and an ``assistant_model`` is
+speculative sampling: the assistant samples the drafts and ``fused.speculative_verify`` (csrc/spec_verify.hip) accepts
+or resamples them, so the tokens are distributed as this model's own samples.
 """
 from __future__ import annotations
 
+import itertools
 import random
 from typing import NamedTuple, Optional
 
@@ -293,9 +296,21 @@ class NativeGenerateMixin:
         temperature, top_k, top_p, seed, step=i)``: the head GEMM and one kernel launch (csrc/lm_sample.hip), no
         [B, V] fp32 tensor and no ``torch.Generator``.  The draw is Gumbel-max on a hash of (seed, step, row, token),
         so a seed gives other tokens than it gives under ``"torch"`` (the default: the warp / softmax / multinomial
-        chain), and top-p keeps or drops equal logits together; ``seed=None`` takes one random seed per call."""
-        if sampler not in ("torch", "fused"):
-            raise ValueError(f"generate: sampler must be 'torch' or 'fused', got {sampler!r}")
+        chain), and top-p keeps or drops equal logits together; ``seed=None`` takes one random seed per call.
+
+        ``sampler="speculative"`` (with ``do_sample=True`` and an ``assistant_model``) is speculative sampling: per
+        round the assistant samples up to ``num_assistant_tokens`` drafts from its own filtered distribution q
+        (``fused.lm_sample``, the same temperature, top-k and top-p), this model scores them in one chunk forward,
+        and ``fused.speculative_verify`` (csrc/spec_verify.hip) keeps draft x with probability min(1, p(x) / q(x)),
+        replaces the first one it drops by a draw from norm(max(0, p - q)) and adds a draw from p when none is
+        dropped.  The tokens are distributed as ``sampler="fused"``'s, whatever the assistant is; they are not the
+        same tokens for a seed.  Both heads' logits must have one dtype for the kernel (else the PyTorch form runs).
+        Returns :class:`SpeculativeOutput` as the greedy path does."""
+        if sampler not in ("torch", "fused", "speculative"):
+            raise ValueError(f"generate: sampler must be 'torch', 'fused' or 'speculative', got {sampler!r}")
+        if sampler == "speculative" and (not do_sample or num_beams != 1 or assistant_model is None):
+            raise ValueError("generate: sampler='speculative' is speculative sampling; it needs do_sample=True, an "
+                             "assistant_model and num_beams=1")
         if sampler == "fused" and (not do_sample or num_beams != 1 or assistant_model is not None):
             raise ValueError("generate: sampler='fused' is the sampling kernel; it needs do_sample=True, num_beams=1 "
                              "and no assistant_model")
@@ -339,7 +354,7 @@ class NativeGenerateMixin:
             if pad_token_id is None:
                 pad_token_id = int(eos[0])
         if assistant_model is not None:
-            if do_sample or num_beams != 1:
+            if (do_sample and sampler != "speculative") or num_beams != 1:
                 raise ValueError("generate: assistant_model is greedy speculative decoding; it needs do_sample=False "
                                  "and num_beams=1 (speculative sampling and assisted beam search are not supported)")
             k = int(num_assistant_tokens)
@@ -359,8 +374,12 @@ class NativeGenerateMixin:
         ids, lens = left_align(input_ids, attention_mask)
         weight = self.lm_head.weight
         if assistant_model is not None:
+            sampling = None
+            if sampler == "speculative":
+                sampling = (float(temperature), int(top_k), float(top_p),
+                            int(seed) if seed is not None else random.getrandbits(63), itertools.count())
             out = self._speculative(assistant_model, input_ids, ids, lens, max_new_tokens, eos, pad_token_id, k,
-                                    kv_cache_dtype, prefill_chunk_size)
+                                    kv_cache_dtype, prefill_chunk_size, sampling)
             fused.check_index_errors()
             return out if return_dict_in_generate else out.sequences
         if num_beams > 1:
@@ -436,13 +455,15 @@ class NativeGenerateMixin:
         return h
 
     def _speculative(self, assistant, input_ids, ids, lens, n, eos, pad_token_id, k, kv_cache_dtype=None,
-                     prefill_chunk_size=None):
-        """Greedy speculative decoding.  Row b has emitted ``count[b]`` tokens, the last of which (``last``) is not
+                     prefill_chunk_size=None, sampling=None):
+        """Speculative decoding: greedy, or with ``sampling`` (temperature, top_k, top_p, seed, step counter)
+        speculative sampling, which differs in how a token is chosen and a draft judged (``_speculative_sample``)
+        and in nothing of the bookkeeping below.  Row b has emitted ``count[b]`` tokens, the last of which (``last``) is not
         in the target's cache yet; the assistant's cache lacks the last one or two of them (``unseen``: two when
         every draft of the previous round was accepted, since the last draft was never fed to the assistant).  A
         round: the assistant absorbs ``unseen`` in a ragged chunk of 2 and drafts kk tokens (kk - 1 single-token
         steps), the target runs one chunk of ``last`` and the drafts, row b keeps the ``a[b]`` drafts that equal the
-        target's top-1 and the target's next token, and both caches are rolled back to what stays valid.  Rows
+        target's top-1 (sampling: that pass the accept test) and the target's next token, and both caches are rolled back to what stays valid.  Rows
         that have emitted EOS or all n tokens are parked at length 0 (their forwards go on, unread).  One host
         read per round: whether a row is still open, and the caches' widths."""
         B, T0 = input_ids.shape
@@ -464,7 +485,11 @@ class NativeGenerateMixin:
             return fused.lm_head_score(flat, w, torch.full((flat.shape[0],), -100, dtype=torch.long, device=dev)).pred.long()
 
         new = torch.zeros(B, n + k + 1, dtype=torch.long, device=dev)
-        last = top1(h, weight)
+        if sampling is None:
+            last = top1(h, weight)
+        else:
+            temperature, top_k, top_p, seed, steps = sampling
+            last = fused.lm_head_sample(h, weight, temperature, top_k, top_p, seed, next(steps)).ids.long()
         new[:, 0] = last
         count = torch.ones(B, dtype=torch.long, device=dev)
         accepted = torch.zeros(B, dtype=torch.long, device=dev)
@@ -485,14 +510,19 @@ class NativeGenerateMixin:
             rounds += 1
             # the assistant: absorb the accepted tokens it has not seen, then draft
             ha = a_base(unseen, cache=a_cache, n_new=n_unseen.to(torch.int32))
-            drafts = [top1(ha[rows, (n_unseen - 1).clamp_min(0)], a_weight)]
-            for _ in range(kk - 1):
-                drafts.append(top1(a_base(drafts[-1][:, None], cache=a_cache)[:, 0], a_weight))
-            drafts = torch.stack(drafts, dim=1)  # [B, kk]
-            # the target: one chunk over the last emitted token and the drafts
-            chunk = torch.cat([last[:, None], drafts], dim=1)
-            pred = top1(base(chunk, cache=cache), weight).view(B, kk + 1)  # the target's token after each of the chunk's inputs
-            a = (pred[:, :kk] == drafts).long().cumprod(1).sum(1)  # accepted drafts
+            ha = ha[rows, (n_unseen - 1).clamp_min(0)]
+            if sampling is None:
+                drafts = [top1(ha, a_weight)]
+                for _ in range(kk - 1):
+                    drafts.append(top1(a_base(drafts[-1][:, None], cache=a_cache)[:, 0], a_weight))
+                drafts = torch.stack(drafts, dim=1)  # [B, kk]
+                # the target: one chunk over the last emitted token and the drafts
+                chunk = torch.cat([last[:, None], drafts], dim=1)
+                pred = top1(base(chunk, cache=cache), weight).view(B, kk + 1)  # the target's token after each of the chunk's inputs
+                a = (pred[:, :kk] == drafts).long().cumprod(1).sum(1)  # accepted drafts
+            else:
+                drafts, pred, a = self._speculative_sample(sampling, ha, lambda t: a_base(t[:, None], cache=a_cache)[:, 0],
+                                                           a_weight, last, lambda c: base(c, cache=cache), weight, kk)
             adv = torch.where(active, torch.minimum(a + 1, n - count), torch.zeros_like(a))
             step = torch.arange(kk + 1, device=dev)
             keep = step[None, :] < adv[:, None]
@@ -526,6 +556,36 @@ class NativeGenerateMixin:
                 n_out = done + 1
         out = torch.cat([input_ids, new[:, :n_out]], dim=1)
         return SpeculativeOutput(out, None, rounds, accepted)
+
+    @staticmethod
+    def _speculative_sample(sampling, ha, a_step, a_weight, last, t_chunk, weight, kk):
+        """One round's drafts and verdict under sampling: (drafts [B, kk], emitted [B, kk + 1], accepted [B]), row b
+        emitting ``drafts[b, :accepted[b]]`` and then the verify's ``next[b]``.  ``ha`` [B, C] is the assistant's
+        hidden state after the last emitted token, ``a_step(tokens)`` its single-token cached step and
+        ``t_chunk(tokens)`` the target's chunk forward.  Every draft step keeps its head's logits and the sampler's
+        floor; the target's ``kk + 1`` rows go through one ``fused.lm_sample`` (their floors, and the bonus token at
+        position kk), then ``fused.speculative_verify``.  Each launch takes the next value of the call's step
+        counter, so the drafts' noise, the target's, the accept uniforms and the residual's are independent."""
+        temperature, top_k, top_p, seed, steps = sampling
+        v = weight.shape[0]
+        drafts, d_logits, d_floor = [], [], []
+        for j in range(kk):
+            if j:
+                ha = a_step(drafts[-1])
+            d_logits.append(fused.lm_head_logits(ha, a_weight))
+            drawn = fused.lm_sample(d_logits[-1], v, temperature, top_k, top_p, seed, next(steps))
+            drafts.append(drawn.ids.long())
+            d_floor.append(drawn.floor)
+        drafts = torch.stack(drafts, dim=1)
+        B = drafts.shape[0]
+        t_logits = fused.lm_head_logits(t_chunk(torch.cat([last[:, None], drafts], dim=1)), weight)  # [B (kk + 1), Vp]
+        drawn = fused.lm_sample(t_logits, v, temperature, top_k, top_p, seed, next(steps))
+        out = fused.speculative_verify(t_logits.view(B, kk + 1, -1), torch.stack(d_logits, dim=1), drafts.to(torch.int32),
+                                       drawn.floor.view(B, kk + 1), torch.stack(d_floor, dim=1),
+                                       drawn.ids.view(B, kk + 1)[:, kk], v, temperature, seed, next(steps))
+        a = out.accepted.long()
+        emitted = torch.cat([drafts, drafts[:, :1]], dim=1).scatter(1, a[:, None], out.next.long()[:, None])
+        return drafts, emitted, a
 
     def _beam_search(self, input_ids, ids, lens, lo, n, eos, pad_token_id, nb, n_ret, length_penalty, early_stopping,
                      kv_cache_dtype=None, prefill_chunk_size=None):

@@ -2498,6 +2498,43 @@ def _lm_sample_torch(logits: torch.Tensor, v: int, inv_t: float, top_k: int, top
     return ids, lse, floor, keep.sum(dim=1).to(torch.int32)
 
 
+def lm_head_logits(h: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
+    """The head's logits ``h @ weight.T`` as [N, Vp] in the compute dtype, the vocabulary padded to a multiple of
+    64 with zero rows (:func:`_pad_rows`): the block the sampling ops read.  Forward only."""
+    with torch.no_grad():
+        h2d = h.reshape(-1, h.shape[-1])
+        if h2d.is_cuda:
+            from .linear import autocast_inputs
+
+            h2d, weight = autocast_inputs(h2d, weight)
+        elif h2d.dtype != weight.dtype:
+            h2d = h2d.to(weight.dtype)
+        with torch.autocast("cuda", enabled=False) if h2d.is_cuda else contextlib.nullcontext():
+            return gemm_fwd(h2d, _pad_rows(weight))
+
+
+def lm_sample(logits: torch.Tensor, v: int, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
+              seed: int = 0, step: int = 0) -> LMSample:
+    """:func:`lm_head_sample` without the GEMM, on a logit block [N, Vp] (real columns j < v) that the caller
+    keeps: speculative sampling needs the draft's rows, and their ``floor``, after the draw.  On the GPU the block
+    is bf16 / fp16 / fp32 with Vp % 8 == 0 (:func:`lm_head_logits` gives such a block) for csrc/lm_sample.hip."""
+    temperature, top_k, top_p = float(temperature), int(top_k), float(top_p)
+    if not temperature > 0 or not 0.0 < top_p <= 1.0 or top_k < 0:
+        raise ValueError(f"dlion: lm_sample needs temperature > 0, 0 < top_p <= 1 and top_k >= 0, got "
+                         f"{temperature}, {top_p}, {top_k}")
+    if logits.dim() != 2 or not 0 < int(v) <= logits.shape[1]:
+        raise ValueError(f"dlion: lm_sample needs logits [N, Vp] and 0 < v <= Vp, got {tuple(logits.shape)}, v = {v}")
+    from .reference import sr_key
+
+    key = sr_key(seed, step)
+    inv_t = torch.tensor(1.0 / temperature, dtype=torch.float32).item()
+    with torch.no_grad():
+        if logits.dtype in _SCORE_DTYPES and _use_hip(logits):
+            with torch.autocast("cuda", enabled=False):
+                return LMSample(*hip.ops().lm_sample(logits.contiguous(), int(v), inv_t, top_k, top_p, key))
+        return LMSample(*_lm_sample_torch(logits, int(v), inv_t, top_k, top_p, key))
+
+
 def lm_head_sample(h: torch.Tensor, weight: torch.Tensor, temperature: float = 1.0, top_k: int = 0,
                    top_p: float = 1.0, seed: int = 0, step: int = 0) -> LMSample:
     """One token per row drawn from the LM head ``h @ weight.T`` after temperature, top-k
@@ -2514,27 +2551,131 @@ def lm_head_sample(h: torch.Tensor, weight: torch.Tensor, temperature: float = 1
     if not temperature > 0 or not 0.0 < top_p <= 1.0 or top_k < 0:
         raise ValueError(f"dlion: lm_head_sample needs temperature > 0, 0 < top_p <= 1 and top_k >= 0, got "
                          f"{temperature}, {top_p}, {top_k}")
+    logits = lm_head_logits(h, weight)  # [N, Vp] in the compute dtype, read-only below
+    return lm_sample(logits, weight.shape[0], temperature, top_k, top_p, seed, step)
+
+
+# --------------------------------------------- speculative sampling: accept / resample (forward only)
+class SpecVerify(NamedTuple):
+    """What :func:`speculative_verify` returns: ``accepted`` [B] (int32, the leading drafts of a row that passed
+    the accept test), ``next`` [B] (int32, the token after them: the residual draw at the first rejection, the bonus
+    token when every draft passed), and per draft position [B, kk] the ``flags`` (int32 1 / 0), the residual token
+    ``resid`` (int32, -1 where the flag is 1), and the draft token's probabilities ``px`` under the target and
+    ``qx`` under the draft (fp32)."""
+
+    accepted: torch.Tensor
+    next: torch.Tensor
+    flags: torch.Tensor
+    resid: torch.Tensor
+    px: torch.Tensor
+    qx: torch.Tensor
+
+
+SPEC_MAX_DRAFTS = 7  # the kernel's kk (csrc/spec_verify.hip): a chunk of the target is at most 8 tokens
+
+
+def sample_uniform(rows: torch.Tensor, key: int, dtype=torch.float64) -> torch.Tensor:
+    """The accept test's uniform of csrc/spec_verify.hip for int64 ``rows`` under the 32-bit ``key``: u = (n + 0.5)
+    2^-24 with n the draw of :func:`sample_gumbel`'s hash in the column slot 0xFFFFFFFF, which no column occupies.
+    Exact in fp64 (the default); fp32 rounds n + 0.5 from n = 2^23 on."""
+    from .reference import _M32, _mix32
+
+    n = _mix32((_mix32(0xFFFFFFFF ^ int(key)) + rows * 0x9E3779B1 + 0x85EBCA6B) & _M32) >> 8
+    return (n.to(dtype) + 0.5) * 2.0 ** -24
+
+
+def _spec_verify_torch(t_logits, d_logits, drafts, t_floor, d_floor, bonus, v: int, inv_t: float, key: int):
+    """PyTorch form of the verify kernel (csrc/spec_verify.hip) in fp32: (accepted, next, flags, resid, px, qx).
+    The survivors' exponentials are fp32 and summed in fp64; the accept test is the exact product u q_x < p_x."""
+    B, kk, _ = d_logits.shape
+    dev = d_logits.device
+    it = torch.tensor(inv_t, dtype=torch.float32, device=dev)
+    ninf = torch.tensor(float("-inf"), device=dev)
+
+    def softmax_over_survivors(x, floor):
+        s = x[..., :v].float() * it
+        alive = torch.isfinite(s) & (s >= floor[..., None])
+        s = torch.where(alive, s, ninf)
+        m = s.max(-1, keepdim=True).values
+        e = torch.where(alive, torch.exp(s - m), torch.zeros_like(s))
+        z = e.sum(-1, keepdim=True, dtype=torch.float64).float()
+        return s, alive, e, z
+
+    sp, alive_p, ep, zp = softmax_over_survivors(t_logits[:, :kk], t_floor[:, :kk])
+    _, alive_q, eq, zq = softmax_over_survivors(d_logits, d_floor)
+    x = drafts.long()
+    inside = (x >= 0) & (x < v)
+    at = x.clamp(0, v - 1)[..., None]
+    zero = torch.zeros((), device=dev)
+    px = torch.where(inside & alive_p.gather(-1, at)[..., 0], (ep.gather(-1, at) / zp)[..., 0], zero)
+    qx = torch.where(inside & alive_q.gather(-1, at)[..., 0], (eq.gather(-1, at) / zq)[..., 0], zero)
+    rows = torch.arange(B * kk, device=dev).view(B, kk)
+    flags = inside & (sample_uniform(rows, key) * qx.double() < px.double())
+    # the residual draw max(0, p - q) by Gumbel-max, then its fallback on the p survivors
+    w = torch.where(alive_p, ep * (1.0 / zp), torch.zeros_like(ep)) - eq * (1.0 / zq).nan_to_num(posinf=0.0)
+    g = sample_gumbel(torch.arange(v, device=dev), rows[..., None], key)
+    score = torch.where(w > 0, torch.log(w.clamp_min(1e-45)) + g, ninf)
+    score = torch.where((w > 0).any(-1, keepdim=True), score, torch.where(alive_p, sp + g, ninf))
+    cols = torch.arange(v, device=dev)
+    best = torch.where(score == score.max(-1, keepdim=True).values, cols, cols.new_full((), v)).min(-1).values
+    best = torch.where(torch.isfinite(score).any(-1), best, torch.full_like(best, -1))
+    resid = torch.where(flags, torch.full_like(best, -1), best).to(torch.int32)
+    accepted = flags.long().cumprod(1).sum(1)
+    nxt = torch.where(accepted == kk, bonus.long(), resid.long().gather(1, accepted.clamp_max(kk - 1)[:, None])[:, 0])
+    return accepted.to(torch.int32), nxt.to(torch.int32), flags.to(torch.int32), resid, px, qx
+
+
+_SPEC_ARRIVE = {}  # (device index, stream) -> the kernel's int32 arrival counters, zero between launches
+
+
+def _spec_arrive(dev: torch.device, batch: int) -> torch.Tensor:
+    key = (dev.index if dev.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(dev).cuda_stream)
+    buf = _SPEC_ARRIVE.get(key)
+    if buf is None or buf.numel() < batch:
+        buf = _SPEC_ARRIVE[key] = torch.zeros(max(batch, 64), dtype=torch.int32, device=dev)
+    return buf
+
+
+def speculative_verify(t_logits: torch.Tensor, d_logits: torch.Tensor, drafts: torch.Tensor, t_floor: torch.Tensor,
+                       d_floor: torch.Tensor, bonus: torch.Tensor, v: int, temperature: float = 1.0, seed: int = 0,
+                       step: int = 0) -> SpecVerify:
+    """The accept / resample step of speculative sampling (Leviathan et al. 2023; Chen et al. 2023) for ``kk``
+    draft tokens per row, ``1 <= kk <= 7``: ``t_logits`` [B, kk + 1, Vp] are the target head's logits of the chunk
+    (the last emitted token, then the drafts), ``d_logits`` [B, kk, Vp] the draft head's logits that ``drafts``
+    [B, kk] were drawn from, ``t_floor`` [B, kk + 1] / ``d_floor`` [B, kk] the ``floor`` that :func:`lm_sample` returned
+    on those rows (they say which columns survived top-k / top-p) and ``bonus`` [B] its draw on target row (b, kk).
+    With p and q the two filtered distributions, draft x passes iff u < p(x) / q(x); the first one that does not
+    is replaced by a draw from norm(max(0, p - q)), so the emitted tokens are distributed as the target's.
+
+    On the GPU with both blocks in one of bf16 / fp16 / fp32 this is one kernel launch (csrc/spec_verify.hip),
+    otherwise (CPU, mixed dtypes, ``set_impl("torch")``) the PyTorch form.  The uniforms and the residual's Gumbel
+    noise are hashes of (``seed``, ``step``, row, token): give this call a ``step`` no sampling call shares.
+    Forward only."""
+    if d_logits.dim() != 3 or t_logits.dim() != 3:
+        raise ValueError("dlion: speculative_verify needs t_logits [B, kk + 1, Vp] and d_logits [B, kk, Vp]")
+    B, kk, vp = d_logits.shape
+    v = int(v)
+    if not 1 <= kk <= SPEC_MAX_DRAFTS or tuple(t_logits.shape) != (B, kk + 1, vp) or not 0 < v <= vp:
+        raise ValueError(f"dlion: speculative_verify needs 1 <= kk <= {SPEC_MAX_DRAFTS}, t_logits [B, kk + 1, Vp] beside "
+                         f"d_logits [B, kk, Vp] and 0 < v <= Vp; got {tuple(t_logits.shape)}, {tuple(d_logits.shape)}, {v}")
+    if (tuple(drafts.shape), tuple(t_floor.shape), tuple(d_floor.shape), tuple(bonus.shape)) != \
+            ((B, kk), (B, kk + 1), (B, kk), (B,)):
+        raise ValueError("dlion: speculative_verify needs drafts [B, kk], t_floor [B, kk + 1], d_floor [B, kk], bonus [B]")
+    temperature = float(temperature)
+    if not temperature > 0:
+        raise ValueError(f"dlion: speculative_verify needs temperature > 0, got {temperature}")
     from .reference import sr_key
 
     key = sr_key(seed, step)
     inv_t = torch.tensor(1.0 / temperature, dtype=torch.float32).item()
     with torch.no_grad():
-        h2d = h.reshape(-1, h.shape[-1])
-        v = weight.shape[0]
-        if h2d.is_cuda:
-            from .linear import autocast_inputs
-
-            h2d, weight = autocast_inputs(h2d, weight)
-        elif h2d.dtype != weight.dtype:
-            h2d = h2d.to(weight.dtype)
-        with torch.autocast("cuda", enabled=False) if h2d.is_cuda else contextlib.nullcontext():
-            logits = gemm_fwd(h2d, _pad_rows(weight))  # [N, Vp] in the compute dtype, read-only below
-            if logits.dtype in _SCORE_DTYPES and _use_hip(logits):
-                out = hip.ops().lm_sample(logits.contiguous(), v, inv_t, top_k, top_p, key)
-            else:
-                out = _lm_sample_torch(logits, v, inv_t, top_k, top_p, key)
-            del logits
-        return LMSample(*out)
+        if t_logits.dtype == d_logits.dtype and d_logits.dtype in _SCORE_DTYPES and _use_hip(d_logits) and t_logits.is_cuda:
+            out = hip.ops().spec_verify(t_logits.contiguous(), d_logits.contiguous(), drafts.to(torch.int32).contiguous(),
+                                        t_floor.float().contiguous(), d_floor.float().contiguous(),
+                                        bonus.to(torch.int32).contiguous(), v, inv_t, key, _spec_arrive(d_logits.device, B))
+        else:
+            out = _spec_verify_torch(t_logits, d_logits, drafts, t_floor.float(), d_floor.float(), bonus, v, inv_t, key)
+    return SpecVerify(*out)
 
 
 def token_predictions(logits, labels=None):

@@ -10,6 +10,8 @@
         --prompt "..." --bf16
     python generate.py --model_name_or_path ./llama-8b --assistant_model ./llama-1b --num_assistant_tokens 5 \\
         --prompt "..." --bf16
+    python generate.py --model_name_or_path ./llama-8b --assistant_model ./llama-1b --do_sample --top_p 0.95 \\
+        --sampler speculative --prompt "..." --bf16
 
 ``--model_name_or_path`` is a named size (random weights, no hub access) or a local HF directory
 (models/registry.py); ``--adapter`` a peft-format LoRA directory as sft_llama2.py writes it.  A directory without a
@@ -44,14 +46,16 @@ def parse_args(argv=None):
     ap.add_argument("--top_k", type=int, default=0)
     ap.add_argument("--top_p", type=float, default=1.0)
     ap.add_argument("--seed", type=int, default=None)
-    ap.add_argument("--sampler", choices=["torch", "fused"], default="torch",
-                    help="with --do_sample: 'fused' draws with the LM-head sampling kernel (fused.lm_head_sample)")
+    ap.add_argument("--sampler", choices=["torch", "fused", "speculative"], default="torch",
+                    help="with --do_sample: 'fused' draws with the LM-head sampling kernel (fused.lm_head_sample); "
+                         "'speculative' (with --assistant_model) is speculative sampling (fused.speculative_verify)")
     ap.add_argument("--num_beams", type=int, default=1, help="beam search (greedy only; HF's semantics)")
     ap.add_argument("--num_return_sequences", type=int, default=1, help="beams returned per prompt, best first")
     ap.add_argument("--length_penalty", type=float, default=1.0)
     ap.add_argument("--early_stopping", action="store_true")
     ap.add_argument("--assistant_model", default=None,
-                    help="a smaller model (name or directory) with the same vocabulary: greedy speculative decoding")
+                    help="a smaller model (name or directory) with the same vocabulary: greedy speculative decoding, "
+                         "or speculative sampling with --do_sample --sampler speculative")
     ap.add_argument("--num_assistant_tokens", type=int, default=5, help="draft tokens per round (1..7)")
     ap.add_argument("--kv_cache_dtype", default=None, choices=("fp8_e4m3",),
                     help="keep the KV cache as e4m3 codes with one scale per (token, kv head): about half the memory")
