@@ -1709,6 +1709,119 @@ Tensor extend_attention(const Tensor& q, const Tensor& k_cache, const Tensor& v_
   return out;
 }
 
+// ---- beam search on a shared prompt cache (csrc/prefix_attention.hip)
+// kv_append with the rotation position (rot_pos, the tables' row) and the suffix cache's index (write_pos) apart
+Tensor kv_append_suffix(const Tensor& q, const Tensor& k, const Tensor& v, const std::optional<Tensor>& rot_pos,
+                        const Tensor& write_pos, const std::optional<Tensor>& cos, const std::optional<Tensor>& sin,
+                        const std::optional<Tensor>& q_gamma, const std::optional<Tensor>& k_gamma, double eps,
+                        const Tensor& k_cache, const Tensor& v_cache, const Tensor& err) {
+  TORCH_CHECK(q.dim() == 3, "dlion kv_append_suffix: q must be [rows, H, D]");
+  const int64_t B = q.size(0), H = q.size(1), D = q.size(2);
+  TORCH_CHECK(D == 64 || D == 128, "dlion kv_append_suffix: head_dim must be 64 or 128");
+  TORCH_CHECK(k.dim() == 3 && v.dim() == 3 && k.size(1) == v.size(1), "dlion kv_append_suffix: k / v must be [rows, Hkv, D]");
+  const int64_t Hkv = k.size(1);
+  TORCH_CHECK(B < (int64_t{1} << 31) / (H + 2 * Hkv), "dlion kv_append_suffix: too many rows");
+  check_step_rows("kv_append_suffix", "q", q, B, D);
+  check_step_rows("kv_append_suffix", "k", k, B, D);
+  check_step_rows("kv_append_suffix", "v", v, B, D);
+  check_cache("kv_append_suffix", "k_cache", k_cache, B, Hkv, D);
+  check_cache("kv_append_suffix", "v_cache", v_cache, B, Hkv, D);
+  const int64_t Ts = k_cache.size(1);
+  TORCH_CHECK(v_cache.size(1) == Ts, "dlion kv_append_suffix: the caches differ in length");
+  TORCH_CHECK(write_pos.is_cuda() && write_pos.scalar_type() == at::kInt && write_pos.is_contiguous() &&
+                  write_pos.numel() == B,
+              "dlion kv_append_suffix: write_pos must be a contiguous int32 [rows] GPU tensor");
+  TORCH_CHECK(err.is_cuda() && err.scalar_type() == at::kInt && err.numel() >= 1,
+              "dlion kv_append_suffix: err must be int32[1]");
+  TORCH_CHECK(cos.has_value() == sin.has_value() && q_gamma.has_value() == k_gamma.has_value() &&
+                  (!q_gamma.has_value() || cos.has_value()),
+              "dlion kv_append_suffix: cos / sin and q_gamma / k_gamma come as pairs, gains only with tables");
+  int64_t n_pos = 0;
+  if (cos.has_value()) {
+    TORCH_CHECK(rot_pos.has_value() && rot_pos->is_cuda() && rot_pos->scalar_type() == at::kInt &&
+                    rot_pos->is_contiguous() && rot_pos->numel() == B,
+                "dlion kv_append_suffix: rot_pos must be a contiguous int32 [rows] GPU tensor");
+    n_pos = cos->dim() == 2 ? cos->size(0) : 0;
+    for (const Tensor* t : {&*cos, &*sin})
+      TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kBFloat16 && t->is_contiguous() && t->dim() == 2 &&
+                      t->size(0) == n_pos && n_pos >= 1 && n_pos < (int64_t{1} << 31) && t->size(1) == D &&
+                      reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                  "dlion kv_append_suffix: cos/sin must be contiguous bf16 [n_pos, D] of one length");
+  }
+  if (q_gamma.has_value())
+    for (const Tensor* g : {&*q_gamma, &*k_gamma})
+      TORCH_CHECK(g->is_cuda() && g->scalar_type() == at::kBFloat16 && g->is_contiguous() && g->numel() == D &&
+                      reinterpret_cast<uintptr_t>(g->data_ptr()) % 16 == 0,
+                  "dlion kv_append_suffix: gains must be contiguous, 16-byte aligned bf16 [D]");
+  const c10::DeviceGuard dg(q.device());
+  auto q_out = at::empty({B, H, D}, q.options());
+  check_hip(dlion::launch_kv_append_suffix(
+                q.data_ptr(), k.data_ptr(), v.data_ptr(), step_row_stride(q), step_row_stride(k), step_row_stride(v),
+                cos.has_value() ? rot_pos->data_ptr<int>() : nullptr, write_pos.data_ptr<int>(),
+                cos.has_value() ? cos->data_ptr() : nullptr, sin.has_value() ? sin->data_ptr() : nullptr,
+                static_cast<int>(n_pos), q_gamma.has_value() ? q_gamma->data_ptr() : nullptr,
+                k_gamma.has_value() ? k_gamma->data_ptr() : nullptr, static_cast<float>(eps), q_out.data_ptr(),
+                k_cache.data_ptr(), v_cache.data_ptr(), cache_batch_stride(k_cache), cache_token_stride(k_cache),
+                cache_batch_stride(v_cache), cache_token_stride(v_cache), static_cast<int>(B), static_cast<int>(H),
+                static_cast<int>(Hkv), static_cast<int>(D), static_cast<int>(Ts), err.data_ptr<int>(), cur_stream()),
+            "kv_append_suffix");
+  return q_out;
+}
+
+// out [Bp nb, H D]; the two (splits, chunk) pairs from ops/fused.py shared_prefix_splits (host bounds only)
+Tensor shared_prefix_attention(const Tensor& q, const Tensor& k_prefix, const Tensor& v_prefix,
+                               const Tensor& prefix_len, const Tensor& k_suffix, const Tensor& v_suffix,
+                               const Tensor& suffix_len, int64_t beams, int64_t window, int64_t max_prefix,
+                               int64_t max_suffix, int64_t splits1, int64_t chunk1, int64_t splits2, int64_t chunk2) {
+  TORCH_CHECK(q.dim() == 3 && k_prefix.dim() == 4 && k_suffix.dim() == 4,
+              "dlion shared_prefix_attention: q must be [Bp nb, H, D], the caches [rows, T, Hkv, D]");
+  const int64_t rows = q.size(0), H = q.size(1), D = q.size(2);
+  const int64_t Bp = k_prefix.size(0), Tp = k_prefix.size(1), Hkv = k_prefix.size(2), Ts = k_suffix.size(1);
+  TORCH_CHECK(D == 64 || D == 128, "dlion shared_prefix_attention: head_dim must be 64 or 128");
+  TORCH_CHECK(Hkv >= 1 && H % Hkv == 0 && H / Hkv <= 8,
+              "dlion shared_prefix_attention: H / Hkv must be an integer in [1, 8]");
+  TORCH_CHECK(beams >= 1 && Bp >= 1 && rows == Bp * beams && beams * (H / Hkv) <= dlion::kPrefixMaxRows,
+              "dlion shared_prefix_attention: q must hold beams rows per prefix row, beams * H / Hkv <= 64");
+  check_step_rows("shared_prefix_attention", "q", q, rows, D);
+  check_cache("shared_prefix_attention", "k_prefix", k_prefix, Bp, Hkv, D);
+  check_cache("shared_prefix_attention", "v_prefix", v_prefix, Bp, Hkv, D);
+  check_cache("shared_prefix_attention", "k_suffix", k_suffix, rows, Hkv, D);
+  check_cache("shared_prefix_attention", "v_suffix", v_suffix, rows, Hkv, D);
+  TORCH_CHECK(v_prefix.size(1) == Tp && v_suffix.size(1) == Ts,
+              "dlion shared_prefix_attention: the k and v caches differ in length");
+  TORCH_CHECK(prefix_len.is_cuda() && prefix_len.scalar_type() == at::kInt && prefix_len.is_contiguous() &&
+                  prefix_len.numel() == Bp && suffix_len.is_cuda() && suffix_len.scalar_type() == at::kInt &&
+                  suffix_len.is_contiguous() && suffix_len.numel() == rows,
+              "dlion shared_prefix_attention: prefix_len / suffix_len must be contiguous int32 [Bp] / [Bp nb] GPU tensors");
+  const int64_t lim = int64_t{1} << 31;
+  TORCH_CHECK(max_prefix >= 1 && max_prefix < lim && max_suffix >= 1 && max_suffix < lim && window >= 0 &&
+                  window < lim && splits1 >= 1 && splits1 <= dlion::kDecodeMaxSplits && chunk1 >= 1 && chunk1 < lim &&
+                  splits2 >= 1 && splits2 <= dlion::kDecodeMaxSplits && chunk2 >= 1 && chunk2 < lim && rows <= 65535 &&
+                  Hkv <= 65535,
+              "dlion shared_prefix_attention: bad bounds / window / splits / chunk / batch");
+  const c10::DeviceGuard dg(q.device());
+  const auto f32 = q.options().dtype(at::kFloat);
+  const int64_t S = splits1 + splits2;
+  auto part_ml = at::empty({2, rows, H, S}, f32);
+  auto part_o = at::empty({rows, H, S, D}, f32);
+  auto out = at::empty({rows, H * D}, q.options());
+  float* pm = part_ml.data_ptr<float>();
+  check_hip(dlion::launch_shared_prefix_attention(
+                q.data_ptr(), step_row_stride(q), k_prefix.data_ptr(), cache_batch_stride(k_prefix),
+                cache_token_stride(k_prefix), v_prefix.data_ptr(), cache_batch_stride(v_prefix),
+                cache_token_stride(v_prefix), prefix_len.data_ptr<int>(), k_suffix.data_ptr(),
+                cache_batch_stride(k_suffix), cache_token_stride(k_suffix), v_suffix.data_ptr(),
+                cache_batch_stride(v_suffix), cache_token_stride(v_suffix), suffix_len.data_ptr<int>(), pm,
+                pm + rows * H * S, part_o.data_ptr<float>(), out.data_ptr(), static_cast<int>(Bp),
+                static_cast<int>(beams), static_cast<int>(H), static_cast<int>(Hkv), static_cast<int>(D),
+                static_cast<int>(Tp), static_cast<int>(Ts), static_cast<int>(max_prefix), static_cast<int>(max_suffix),
+                static_cast<int>(window), static_cast<int>(splits1), static_cast<int>(chunk1),
+                static_cast<int>(splits2), static_cast<int>(chunk2), 1.0f / std::sqrt(static_cast<float>(D)),
+                cur_stream()),
+            "shared_prefix_attention");
+  return out;
+}
+
 // ---- generation on an fp8 KV cache (csrc/kv8_attention.hip, the fp8 appends of decode.hip / chunk_attention.hip)
 // codes [B, Tmax, Hkv, D] uint8, token-major with contiguous heads and 16-byte aligned token / batch strides;
 // scales [B, Tmax, Hkv] fp32 with contiguous heads
@@ -2025,6 +2138,11 @@ TORCH_LIBRARY(dlion, m) {
         " int max_len, int splits, int chunk) -> Tensor");
   m.def("extend_attention(Tensor q, Tensor k_cache, Tensor v_cache, Tensor kv_len, Tensor? n_new, int window,"
         " int max_len, int splits, int chunk) -> Tensor");
+  m.def("kv_append_suffix(Tensor q, Tensor k, Tensor v, Tensor? rot_pos, Tensor write_pos, Tensor? cos, Tensor? sin,"
+        " Tensor? q_gamma, Tensor? k_gamma, float eps, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor(c!) err) -> Tensor");
+  m.def("shared_prefix_attention(Tensor q, Tensor k_prefix, Tensor v_prefix, Tensor prefix_len, Tensor k_suffix,"
+        " Tensor v_suffix, Tensor suffix_len, int beams, int window, int max_prefix, int max_suffix, int splits1,"
+        " int chunk1, int splits2, int chunk2) -> Tensor");
   m.def("kv_quantize(Tensor x, Tensor(a!) codes, Tensor(b!) scales) -> ()");
   m.def("kv_append_fp8(Tensor q, Tensor k, Tensor v, Tensor pos, Tensor? cos, Tensor? sin, Tensor? q_gamma,"
         " Tensor? k_gamma, float eps, Tensor(a!) k_codes, Tensor(b!) v_codes, Tensor(c!) k_scales, Tensor(d!) v_scales,"
@@ -2181,6 +2299,8 @@ TORCH_LIBRARY_IMPL(dlion, CUDA, m) {
   m.impl("decode_attention", &decode_attention);
   m.impl("kv_append_chunk", &kv_append_chunk);
   m.impl("chunk_attention", &chunk_attention);
+  m.impl("kv_append_suffix", &kv_append_suffix);
+  m.impl("shared_prefix_attention", &shared_prefix_attention);
   m.impl("extend_attention", &extend_attention);
   m.impl("kv_quantize", &kv_quantize);
   m.impl("kv_append_fp8", &kv_append_fp8);

@@ -248,6 +248,33 @@ hipError_t launch_chunk_attention(const void* q, const void* k_cache, int64_t k_
 hipError_t launch_chunk_combine(const float* part_m, const float* part_l, const float* part_o, void* out,
                                 int64_t rows, int D, int splits, hipStream_t st);
 
+// ---- beam search on a shared prompt cache (prefix_attention.hip); bf16, D in {64, 128}, nb H / Hkv <= kPrefixMaxRows
+// launch_kv_append with two positions per row: q / k of row r are normed / rotated at rot_pos[r] (tables [n_pos, D];
+// rot_pos may be null without tables) and k, v written to cache[r, write_pos[r]] of the suffix caches [rows, Ts, Hkv,
+// D].  A write position outside [0, Ts) ORs kIndexErrCache into err[0] and nothing is written to the caches; a
+// rotation position outside [0, n_pos) ORs it too and is clamped.  q_out [rows, H, D].
+constexpr int kPrefixMaxRows = 64;
+hipError_t launch_kv_append_suffix(const void* q, const void* k, const void* v, int64_t q_ld, int64_t k_ld,
+                                   int64_t v_ld, const int* rot_pos, const int* write_pos, const void* cos,
+                                   const void* sin, int n_pos, const void* q_gamma, const void* k_gamma, float eps,
+                                   void* q_out, void* k_cache, void* v_cache, int64_t kc_bs, int64_t kc_ts,
+                                   int64_t vc_bs, int64_t vc_ts, int rows, int H, int Hkv, int D, int Ts,
+                                   int32_t* err, hipStream_t st);
+// out [Bp nb, H D]: row r = b nb + j attends the keys [0, plen) of prefix row b and then [0, slen) of its own suffix
+// row, plen = min(prefix_len[b], max_prefix, Tp), slen = min(suffix_len[r], max_suffix, Ts); under a window the key
+// at total position t is visible iff t >= plen + slen - window.  splits1 blocks of chunk1 keys per (kv head, prompt)
+// over the prefix, splits1 chunk1 >= min(window, max_prefix); splits2 blocks of chunk2 keys per (kv head, row) over
+// the suffix, splits2 chunk2 >= min(window, max_suffix).  fp32 partials part_m / part_l [Bp nb, H, splits1 +
+// splits2], part_o [.., D]: the prefix slots first, reduced in index order by launch_chunk_combine.
+hipError_t launch_shared_prefix_attention(const void* q, int64_t q_ld, const void* k_prefix, int64_t kp_bs,
+                                          int64_t kp_ts, const void* v_prefix, int64_t vp_bs, int64_t vp_ts,
+                                          const int* prefix_len, const void* k_suffix, int64_t ks_bs, int64_t ks_ts,
+                                          const void* v_suffix, int64_t vs_bs, int64_t vs_ts, const int* suffix_len,
+                                          float* part_m, float* part_l, float* part_o, void* out, int Bp, int nb,
+                                          int H, int Hkv, int D, int Tp, int Ts, int max_prefix, int max_suffix,
+                                          int window, int splits1, int chunk1, int splits2, int chunk2, float scale,
+                                          hipStream_t st);
+
 // ---- generation, any T tokens per sequence (extend_attention.hip); bf16, D in {64, 128}
 // launch_chunk_attention's semantics without its limit on T.  A block owns kExtendTQ consecutive tokens of one kv
 // head and one key split; splits blocks of chunk keys per (token tile, kv head, row), splits chunk >=

@@ -39,6 +39,7 @@ from ..ops.linear import gemm_fwd
 
 _EOS_CHECK_EVERY = 8  # decode steps between two host reads of "every row has finished"
 KV_CACHE_DTYPES = (None, "fp8_e4m3")  # None: the model's dtype
+BEAM_CACHES = ("repeated", "shared")  # beam search: a private copy of the prompt's cache per beam, or one per prompt
 
 
 class GenerateOutput(NamedTuple):
@@ -199,6 +200,45 @@ class KVCache:
         self.lengths.copy_(self.lengths.index_select(0, index))
 
 
+class BeamKVCache:
+    """Beam search on a shared prompt cache: ``prefix``, the prefilled ``KVCache`` of the B prompts exactly as the
+    prefill left it (its width is the prompt's, no room for new tokens), and ``suffix``, a ``KVCache`` of ``B * beams``
+    rows and ``max_new_tokens`` positions for what the beams generate.  Beam row ``r = b * beams + j`` attends prompt
+    b's prefix keys and its own suffix keys (``fused.kv_append_suffix`` / ``fused.shared_prefix_attention``,
+    csrc/prefix_attention.hip): no prompt key is copied.  The models drive it through ``begin`` / ``advance`` like a
+    ``KVCache``, for single-token steps only."""
+
+    def __init__(self, prefix: KVCache, beams: int, max_new_tokens: int, config, dtype=torch.float32):
+        if not prefix.prefilled or prefix.kv_dtype is not None:
+            raise ValueError("BeamKVCache: the prefix must be a prefilled cache in the model's dtype")
+        self.prefix, self.beams = prefix, int(beams)
+        if self.beams < 2:
+            raise ValueError("BeamKVCache: beams must be >= 2")
+        self.batch = prefix.batch * self.beams
+        dev = prefix.lengths.device
+        self.suffix = KVCache(config, self.batch, max_new_tokens, dev, dtype)
+        self.suffix.prefilled = True  # empty rows that take single-token steps
+        self.max_len = prefix.max_len + self.suffix.max_len  # the positions a rotary table must cover
+        self.prefix_len = prefix.lengths  # int32 [B]
+        self._base = prefix.lengths.repeat_interleave(self.beams)
+        self.positions = self._base  # int32 [B * beams]: the total position of the token of the step in flight
+
+    def begin(self, B: int, T: int, n_new: Optional[torch.Tensor] = None, extend: bool = False) -> bool:
+        """Start a decode step of one token per beam row; never the prefill (always False)."""
+        if T != 1 or n_new is not None or extend:
+            raise ValueError("BeamKVCache: a forward takes one token per beam row (no chunks, no extend)")
+        self.suffix.begin(B, 1)
+        self.positions = self._base + self.suffix.lengths
+        return False
+
+    def advance(self, T: int) -> None:
+        self.suffix.advance(T)
+
+    def reorder_rows(self, index: torch.Tensor) -> None:
+        """Beam row r continues beam ``index[r]`` of the same prompt: only the suffix moves."""
+        self.suffix.reorder_rows(index)
+
+
 # ------------------------------------------------------------------------------------------ prompts
 def left_align(input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor]):
     """(ids with every row's tokens moved to the left edge, lengths [B]); the mask may be left- or right-padded
@@ -255,7 +295,7 @@ class NativeGenerateMixin:
                  seed: Optional[int] = None, num_beams: int = 1, num_return_sequences: int = 1,
                  length_penalty: float = 1.0, early_stopping: bool = False, return_dict_in_generate: bool = False,
                  assistant_model=None, num_assistant_tokens: int = 5, kv_cache_dtype: Optional[str] = None,
-                 prefill_chunk_size: Optional[int] = None, sampler: str = "torch"):
+                 prefill_chunk_size: Optional[int] = None, sampler: str = "torch", beam_cache: str = "repeated"):
         """[B, T0] prompts -> [B, T0 + n_new] long: the prompt exactly as given, then the new tokens.
 
         Greedy takes the top-1 of ``fused.lm_head_score`` (the lowest id on ties, no [B, V] tensor); sampling
@@ -305,7 +345,18 @@ class NativeGenerateMixin:
         replaces the first one it drops by a draw from norm(max(0, p - q)) and adds a draw from p when none is
         dropped.  The tokens are distributed as ``sampler="fused"``'s, whatever the assistant is; they are not the
         same tokens for a seed.  Both heads' logits must have one dtype for the kernel (else the PyTorch form runs).
-        Returns :class:`SpeculativeOutput` as the greedy path does."""
+        Returns :class:`SpeculativeOutput` as the greedy path does.
+
+        ``beam_cache="shared"`` (with ``num_beams > 1``) keeps the prompt's keys and values once per prompt instead
+        of once per beam: a :class:`BeamKVCache` of the prefill's cache (allocated at the prompt's width) and a suffix
+        cache of ``B * num_beams`` rows for the generated tokens; every step runs ``fused.kv_append_suffix`` and
+        ``fused.shared_prefix_attention`` (csrc/prefix_attention.hip), whose prefix blocks stream a prompt's keys once
+        for all its beams.  The cache takes ``T0 + num_beams * max_new_tokens`` positions per prompt instead of
+        ``num_beams * (T0 + max_new_tokens)``.  The same search; the scores differ from the default's by rounding.
+        It needs the model's dtype for the cache and ``num_beams * H / Hkv <= 64``.  Default ``"repeated"``: one
+        private copy of the prompt's cache per beam (``KVCache.repeat_rows``)."""
+        if beam_cache not in BEAM_CACHES:
+            raise ValueError(f"generate: beam_cache must be one of {BEAM_CACHES}, got {beam_cache!r}")
         if sampler not in ("torch", "fused", "speculative"):
             raise ValueError(f"generate: sampler must be 'torch', 'fused' or 'speculative', got {sampler!r}")
         if sampler == "speculative" and (not do_sample or num_beams != 1 or assistant_model is None):
@@ -328,6 +379,17 @@ class NativeGenerateMixin:
                              + (" (more than one sequence per prompt needs num_beams > 1)" if num_beams == 1 else ""))
         if num_beams > 1 and do_sample:
             raise ValueError("generate: num_beams > 1 with do_sample=True (beam sampling) is not supported")
+        if beam_cache == "shared":
+            if num_beams == 1:
+                raise ValueError("generate: beam_cache='shared' shares a prompt's cache among beams; it needs num_beams > 1")
+            if kv_cache_dtype is not None:
+                raise ValueError(f"generate: beam_cache='shared' keeps the cache in the model's dtype; kv_cache_dtype="
+                                 f"{kv_cache_dtype!r} is not supported with it")
+            group = cache_geometry(self.config)
+            heads = self.config.n_head if self.config.model_type == "gpt2" else self.config.num_attention_heads
+            if num_beams * (heads // group[1]) > fused.PREFIX_MAX_ROWS:
+                raise ValueError(f"generate: beam_cache='shared' serves num_beams * H / Hkv <= {fused.PREFIX_MAX_ROWS} "
+                                 f"query rows per prompt and kv head, got {num_beams} * {heads // group[1]}")
         if not isinstance(early_stopping, bool):
             raise ValueError(f"generate: early_stopping must be False or True, got {early_stopping!r}")
         if self.training:
@@ -386,7 +448,7 @@ class NativeGenerateMixin:
             lo = T0 if attention_mask is None else int(lens.min())
             out = self._beam_search(input_ids, ids, lens, lo, max_new_tokens, eos, pad_token_id, num_beams,
                                     num_return_sequences, float(length_penalty), early_stopping, kv_cache_dtype,
-                                    prefill_chunk_size)
+                                    prefill_chunk_size, beam_cache == "shared")
             fused.check_index_errors()
             return out if return_dict_in_generate else out.sequences
         cache = KVCache(cfg, B, total, dev, weight.dtype, kv_cache_dtype)
@@ -588,14 +650,15 @@ class NativeGenerateMixin:
         return drafts, emitted, a
 
     def _beam_search(self, input_ids, ids, lens, lo, n, eos, pad_token_id, nb, n_ret, length_penalty, early_stopping,
-                     kv_cache_dtype=None, prefill_chunk_size=None):
+                     kv_cache_dtype=None, prefill_chunk_size=None, shared=False):
         """transformers' ``GenerationMixin._beam_search`` on the native cache: the same running / finished beam
         sets, scores and stopping rules, with two differences in mechanics.  The candidates of a step are the
         ``keep`` best continuations of every beam (``fused.lm_head_topk``: values - logsumexp are the
         log-probabilities) instead of a [B, num_beams * V] log-softmax -- a beam's continuation outside its own
         best ``keep`` cannot be among the batch row's best ``keep``.  And the prompt is prefilled once per row,
         its cache rows repeated (``KVCache.repeat_rows``), and every step moves only the generated suffix
-        between the beams of a row (``KVCache.reorder_rows``).  One host read per step (HF reads the same flag)."""
+        between the beams of a row (``KVCache.reorder_rows``).  One host read per step (HF reads the same flag).
+        ``shared``: the prefill's cache is not repeated; the beams share it through a :class:`BeamKVCache`."""
         B, T0 = input_ids.shape
         dev = input_ids.device
         cfg, weight, base = self.config, self.lm_head.weight, self._decoder()
@@ -605,9 +668,9 @@ class NativeGenerateMixin:
                              f"{min(fused.LM_TOPK_MAX, cfg.vocab_size)} (the top-k kernel's k, the vocabulary) fit")
         fill = pad_token_id if pad_token_id is not None else 0
         rows = torch.arange(B, device=dev)
-        first = KVCache(cfg, B, T0 + n, dev, weight.dtype, kv_cache_dtype)
+        first = KVCache(cfg, B, T0 if shared else T0 + n, dev, weight.dtype, kv_cache_dtype)
         h = self._prefill(base, ids, lens, first, prefill_chunk_size)  # one prefill per prompt
-        cache = first.repeat_rows(nb)
+        cache = BeamKVCache(first, nb, n, cfg, weight.dtype) if shared else first.repeat_rows(nb)
         del first
         h = h.repeat_interleave(nb, dim=0)
 
@@ -661,7 +724,10 @@ class NativeGenerateMixin:
             go_on = torch.any(unsat) & ~(torch.all(fin_done) & (early_stopping is True)) & ~torch.all(hits)
             if not bool(go_on):  # the one host read of the step
                 break
-            cache.reorder_rows(beam_idx, lo)
+            if shared:
+                cache.reorder_rows(beam_idx)
+            else:
+                cache.reorder_rows(beam_idx, lo)
             h = base(run_seq[:, :, i].reshape(-1, 1), cache=cache)[:, 0]
         seqs = fin_seq[:, :n_ret].reshape(B * n_ret, n)
         n_new = int(fin_len[:, :n_ret].max())

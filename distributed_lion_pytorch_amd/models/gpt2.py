@@ -29,7 +29,7 @@ from transformers.modeling_outputs import CausalLMOutputWithCrossAttentions
 
 from ..ops import fused
 from ..ops.linear import linear_kn, no_wgrad_deferral_this_window
-from .generation import NativeGenerateMixin
+from .generation import BeamKVCache, NativeGenerateMixin
 from .loss_options import LossOptionsMixin
 from .scoring import scored_output
 
@@ -91,9 +91,17 @@ class Attention(nn.Module):
         (``extend``: any T, fused.extend_attention above 8 tokens per row)."""
         B, T, C = x.shape
         H, D = self.n_head, self.head_dim
+        qkv = self.c_attn(x)
+        if isinstance(cache, BeamKVCache):
+            # beam search on a shared prompt cache: a decode step whose rows attend their prompt's prefix cache row
+            # and their own suffix row
+            (kp, vp), (kc, vc), sfx = cache.prefix.layer(self.layer_idx), cache.suffix.layer(self.layer_idx), cache.suffix
+            q, k, v = (qkv[:, 0, j * C:(j + 1) * C].view(B, H, D) for j in range(3))
+            q = fused.kv_append_suffix(q, k, v, None, sfx.lengths, None, None, None, None, 0.0, kc, vc)
+            return fused.shared_prefix_attention(q, kp, vp, cache.prefix_len, kc, vc, sfx.kv_len, cache.beams, 0,
+                                                 cache.prefix.width, sfx.width + 1).view(B, 1, C)
         kc, vc = cache.layer(self.layer_idx)
         ks, vs = cache.layer_scales(self.layer_idx)  # an fp8 cache: kc / vc are codes
-        qkv = self.c_attn(x)
         if cache.prefilled and cache.chunk:
             q, k, v = (qkv[..., j * C:(j + 1) * C].view(B, T, H, D) for j in range(3))
             q = fused.kv_append_chunk(q, k, v, cache.lengths, None, None, None, None, 0.0, kc, vc, cache.n_new, ks, vs)
@@ -201,6 +209,8 @@ class GPT2Model(nn.Module):
         B, T = input_ids.shape
         if cache.begin(B, T, n_new, extend):
             x = fused.embed(input_ids, self.wte.weight, self.wpe.weight, 0.0)
+        elif isinstance(cache, BeamKVCache):  # the learned position is the total one: prompt length + suffix index
+            x = F.embedding(input_ids, self.wte.weight) + F.embedding(cache.positions.long(), self.wpe.weight)[:, None]
         elif cache.chunk:
             pos = fused.chunk_positions(cache.lengths, T, cache.n_new, self.wpe.weight.shape[0])
             x = F.embedding(input_ids, self.wte.weight) + F.embedding(pos, self.wpe.weight)

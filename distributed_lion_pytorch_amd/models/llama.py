@@ -21,7 +21,7 @@ from transformers.modeling_outputs import CausalLMOutputWithPast
 
 from ..ops import fused
 from ..ops.linear import linear_multi_nk, linear_nk, no_wgrad_deferral_this_window
-from .generation import NativeGenerateMixin
+from .generation import BeamKVCache, NativeGenerateMixin
 from .loss_options import LossOptionsMixin
 from .scoring import scored_output
 
@@ -201,10 +201,21 @@ class LlamaAttention(nn.Module):
         fused.decode_attention reads the cache once for the whole group of query heads.  ``extend``: a forward of
         any T after the prefill, fused.extend_attention above 8 tokens per row."""
         B, T, _ = x.shape
-        kc, vc = cache.layer(self.layer_idx)
-        ks, vs = cache.layer_scales(self.layer_idx)  # an fp8 cache: kc / vc are codes
         q, k, v = _proj(x, (self.q_proj, self.k_proj, self.v_proj))
         gq, gk, eps = (self.q_norm.weight, self.k_norm.weight, self.q_norm.eps) if hasattr(self, "q_norm") else (None, None, 0.0)
+        if isinstance(cache, BeamKVCache):
+            # beam search on a shared prompt cache: a decode step whose rows attend their prompt's prefix cache row
+            # and their own suffix row; the token is rotated at its total position and written at its suffix index
+            (kp, vp), (kc, vc), sfx = cache.prefix.layer(self.layer_idx), cache.suffix.layer(self.layer_idx), cache.suffix
+            q = q[:, 0].view(B, self.n_head, self.head_dim)
+            k = k[:, 0].view(B, self.n_kv, self.head_dim)
+            v = v[:, 0].view(B, self.n_kv, self.head_dim)
+            q = fused.kv_append_suffix(q, k, v, cache.positions, sfx.lengths, cos, sin, gq, gk, eps, kc, vc)
+            y = fused.shared_prefix_attention(q, kp, vp, cache.prefix_len, kc, vc, sfx.kv_len, cache.beams, self.window,
+                                              cache.prefix.width, sfx.width + 1)
+            return _lin(self.o_proj, y.view(B, 1, -1))
+        kc, vc = cache.layer(self.layer_idx)
+        ks, vs = cache.layer_scales(self.layer_idx)  # an fp8 cache: kc / vc are codes
         if cache.prefilled and cache.chunk:
             # T tokens per row (1 < T <= 8, any T with extend, or ragged): token t at position lengths[b] + t, causal
             # inside the chunk

@@ -1483,6 +1483,156 @@ def chunk_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tenso
     return chunk_attention_reference(q, k_cache, v_cache, kv_len, n_new, window, max_len)
 
 
+# Beam search on a shared prompt cache (csrc/prefix_attention.hip): the nb beams of a prompt share one prefix cache
+# row and own one suffix cache row each.
+PREFIX_MAX_ROWS = 64  # csrc/kernels.h kPrefixMaxRows: beams * H / Hkv query rows ride in one block's MFMA tiles
+
+
+def shared_prefix_splits(Bp: int, beams: int, Hkv: int, max_prefix: int, max_suffix: int, window: int = 0, splits=None):
+    """((S1, chunk1), (S2, chunk2)): ``decode_splits`` for the prefix grid (one block per split, kv head and prompt;
+    a prompt's visible prefix keys span at most ``min(window, max_prefix)``) and for the suffix grid (per split, kv
+    head and beam row).  Host bounds only.  ``splits=(S1, S2)`` forces the counts (tests)."""
+    s1, s2 = (None, None) if splits is None else splits
+    return (decode_splits(Bp, Hkv, max_prefix, window, s1), decode_splits(Bp * beams, Hkv, max_suffix, window, s2))
+
+
+def kv_append_suffix_reference(q, k, v, rot_pos, write_pos, cos, sin, q_gamma, k_gamma, eps, k_cache,
+                               v_cache) -> torch.Tensor:
+    """The PyTorch form of kv_append_suffix (same arguments): ``kv_append_reference``'s chain with the tables' row
+    ``rot_pos[r]`` and the cache index ``write_pos[r]`` apart; a row whose write position is outside the cache is
+    not written."""
+    Ts = k_cache.shape[1]
+    w = write_pos.long()
+    inside = (w >= 0) & (w < Ts)
+    bad = ~inside.all()
+    if cos is not None:
+        p = rot_pos.long()
+        bad = bad | ((p < 0) | (p >= cos.shape[0])).any()
+        p = p.clamp(0, cos.shape[0] - 1)
+    if w.is_cuda:
+        _index_flag(w.device).bitwise_or_(bad.to(torch.int32) * _IDX_CACHE)
+    elif bool(bad):
+        raise _index_error(_IDX_CACHE, "kv_append_suffix")
+    if cos is not None:
+        c, s = cos[p], sin[p]
+        if q_gamma is not None:
+            def normed(x, gamma):
+                xf = x if x.dtype == torch.float64 else x.float()
+                return gamma * (xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps)).to(x.dtype)
+
+            q, k = normed(q, q_gamma), normed(k, k_gamma)
+        q, k = _rope_rows(q, c, s), _rope_rows(k, c, s)
+    rows = torch.arange(w.shape[0], device=w.device)[inside]
+    k_cache[rows, w[inside]] = k[inside].to(k_cache.dtype)
+    v_cache[rows, w[inside]] = v[inside].to(v_cache.dtype)
+    return q.contiguous()
+
+
+def kv_append_suffix(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, rot_pos, write_pos: torch.Tensor, cos, sin,
+                     q_gamma, k_gamma, eps: float, k_cache: torch.Tensor, v_cache: torch.Tensor) -> torch.Tensor:
+    """``kv_append`` for a beam's suffix cache [rows, Ts, Hkv, D]: q and k of row r are normed / rotated at the total
+    position ``rot_pos[r]`` (prefix length + suffix index; int32 [rows], unused and may be None without tables) --
+    bit for bit ``kv_append`` at that position -- and k, v are written to ``cache[r, write_pos[r]]``.  A write position
+    outside [0, Ts) writes nothing to the caches, a rotation position outside the tables is clamped; both raise through
+    check_index_errors (on the CPU: at once).  bf16 at head_dim 64 / 128 runs csrc/prefix_attention.hip."""
+    if (cos is None) != (sin is None) or (q_gamma is None) != (k_gamma is None) or (q_gamma is not None and cos is None):
+        raise ValueError("kv_append_suffix: cos / sin and q_gamma / k_gamma come as pairs, gains only with tables")
+    if cos is not None and rot_pos is None:
+        raise ValueError("kv_append_suffix: the tables need rot_pos")
+    D = q.shape[-1]
+    if (q.dtype == k.dtype == v.dtype == torch.bfloat16 and D in (64, 128) and q.is_cuda and write_pos.is_cuda
+            and write_pos.dtype == torch.int32 and _cache_ok(k_cache) and _cache_ok(v_cache)
+            and q.shape[0] * (q.shape[1] + 2 * k.shape[1]) < (1 << 31)
+            and (cos is None or (rot_pos.is_cuda and rot_pos.dtype == torch.int32 and cos.shape == sin.shape
+                                 and all(t.dtype == torch.bfloat16 and t.dim() == 2 for t in (cos, sin))))
+            and (q_gamma is None or all(g.dtype == torch.bfloat16 and g.is_contiguous() and g.data_ptr() % 16 == 0
+                                        for g in (q_gamma, k_gamma)))
+            and _use_hip(q)):
+        q, k, v = (t if _step_rows_ok(t) else t.contiguous() for t in (q, k, v))
+        if cos is not None:
+            cos, sin, rot_pos = cos.contiguous(), sin.contiguous(), rot_pos.contiguous()
+        return hip.ops().kv_append_suffix(q, k, v, rot_pos if cos is not None else None, write_pos.contiguous(), cos, sin,
+                                          q_gamma, k_gamma, float(eps), k_cache, v_cache, _index_flag(q.device))
+    return kv_append_suffix_reference(q, k, v, rot_pos, write_pos, cos, sin, q_gamma, k_gamma, eps, k_cache, v_cache)
+
+
+def _prefix_bounds(k_prefix, k_suffix, max_prefix, max_suffix):
+    Tp, Ts = k_prefix.shape[1], k_suffix.shape[1]
+    return (Tp if max_prefix is None else max(1, min(int(max_prefix), Tp)),
+            Ts if max_suffix is None else max(1, min(int(max_suffix), Ts)))
+
+
+def shared_prefix_attention_reference(q, k_prefix, v_prefix, prefix_len, k_suffix, v_suffix, suffix_len, beams: int,
+                                      window: int = 0, max_prefix=None, max_suffix=None) -> torch.Tensor:
+    """The PyTorch form of shared_prefix_attention (same arguments): masked softmax attention of one query per beam
+    row over its prompt's prefix keys followed by its own suffix keys, in fp32 (fp64 inputs stay fp64).  Cache
+    elements outside a row's key range are replaced by zeros before they enter a product, so whatever they hold (NaN
+    included) cannot reach the output."""
+    rows, H, D = q.shape
+    Hkv, nb = k_prefix.shape[2], int(beams)
+    Lp, Ls = _prefix_bounds(k_prefix, k_suffix, max_prefix, max_suffix)
+    npre = prefix_len.long().clamp(0, Lp).repeat_interleave(nb)  # [rows]
+    nsuf = suffix_len.long().clamp(0, Ls)
+    jp, js = torch.arange(Lp, device=q.device), torch.arange(Ls, device=q.device)
+    vis_p, vis_s = jp[None, :] < npre[:, None], js[None, :] < nsuf[:, None]
+    if window:
+        edge = (npre + nsuf - int(window))[:, None]  # the first visible total position
+        vis_p, vis_s = vis_p & (jp[None, :] >= edge), vis_s & (npre[:, None] + js[None, :] >= edge)
+    ct = torch.float64 if q.dtype == torch.float64 else torch.float32
+    zero = torch.zeros((), dtype=ct, device=q.device)
+    visible = torch.cat([vis_p, vis_s], dim=1)  # [rows, Lp + Ls]
+    used_p = vis_p.view(-1, nb, Lp).any(1)  # [Bp, Lp]: prefix keys some beam of the prompt attends
+
+    def keys(pre, suf):
+        pre = torch.where(used_p[:, :, None, None], pre[:, :Lp].to(ct), zero).repeat_interleave(nb, dim=0)
+        return torch.cat([pre, torch.where(vis_s[:, :, None, None], suf[:, :Ls].to(ct), zero)], dim=1)
+
+    kf, vf = keys(k_prefix, k_suffix), keys(v_prefix, v_suffix)
+    qf = q.to(ct).reshape(rows, Hkv, H // Hkv, D)
+    s = torch.einsum("bkgd,btkd->bkgt", qf, kf) * (1.0 / D ** 0.5)
+    vis = visible[:, None, None, :]
+    s = s.masked_fill(~vis, float("-inf"))
+    P = torch.softmax(s, dim=-1)
+    P = torch.where(vis.any(-1, keepdim=True), P, zero)  # a row without keys: zeros, not 0 / 0
+    return torch.einsum("bkgt,btkd->bkgd", P, vf).reshape(rows, H * D).to(q.dtype)
+
+
+def shared_prefix_attention(q: torch.Tensor, k_prefix: torch.Tensor, v_prefix: torch.Tensor, prefix_len: torch.Tensor,
+                            k_suffix: torch.Tensor, v_suffix: torch.Tensor, suffix_len: torch.Tensor, beams: int,
+                            window: int = 0, max_prefix=None, max_suffix=None, splits=None) -> torch.Tensor:
+    """q [Bp * beams, H, D] (one new query per beam), prefix caches [Bp, Tp, Hkv, D] with prefix_len int32 [Bp],
+    suffix caches [Bp * beams, Ts, Hkv, D] with suffix_len int32 [Bp * beams] (the token just appended included)
+    -> [Bp * beams, H * D]: row ``r = b * beams + j`` attends the prefix keys ``[0, prefix_len[b])`` of prompt b and
+    then the suffix keys ``[0, suffix_len[r])`` of its own row; with ``window`` > 0 only the keys at total positions
+    ``>= prefix_len[b] + suffix_len[r] - window``.  A row without a visible key is zero.  ``max_prefix`` /
+    ``max_suffix`` are host bounds on the lengths (default: the cache widths): they size the grids without a device
+    sync and the lengths are clamped to them.  bf16 at head_dim 64 / 128 with H / Hkv in 1..8 and ``beams * H / Hkv
+    <= 64`` runs csrc/prefix_attention.hip: a block streams a chunk of one prompt's prefix keys once for all its
+    beams' query heads (MFMA), a VALU block per beam row covers the suffix, both write fp32 partials into one buffer
+    (prefix slots first) and one combine pass reduces them in index order, no atomics.  Anything else runs the PyTorch
+    form.  ``splits=(S1, S2)`` forces the split counts."""
+    rows, H, D = q.shape
+    Bp, Hkv, nb = k_prefix.shape[0], k_prefix.shape[2], int(beams)
+    if nb < 1 or rows != Bp * nb or k_suffix.shape[0] != rows:
+        raise ValueError(f"shared_prefix_attention: {rows} query rows and {k_suffix.shape[0]} suffix rows for "
+                         f"{Bp} prefix rows of {nb} beams")
+    window = int(window or 0)
+    max_prefix, max_suffix = _prefix_bounds(k_prefix, k_suffix, max_prefix, max_suffix)
+    if (q.dtype == torch.bfloat16 and D in (64, 128) and H % Hkv == 0 and 1 <= H // Hkv <= 8
+            and nb * (H // Hkv) <= PREFIX_MAX_ROWS and q.is_cuda and window < (1 << 30)
+            and all(t.is_cuda and t.dtype == torch.int32 for t in (prefix_len, suffix_len))
+            and all(_cache_ok(c) for c in (k_prefix, v_prefix, k_suffix, v_suffix))
+            and rows <= 65535 and Hkv <= 65535 and _use_hip(q)):
+        if not _step_rows_ok(q):
+            q = q.contiguous()
+        (s1, c1), (s2, c2) = shared_prefix_splits(Bp, nb, Hkv, max_prefix, max_suffix, window, splits)
+        return hip.ops().shared_prefix_attention(q, k_prefix, v_prefix, prefix_len.contiguous(), k_suffix, v_suffix,
+                                                 suffix_len.contiguous(), nb, window, max_prefix, max_suffix, s1, c1,
+                                                 s2, c2)
+    return shared_prefix_attention_reference(q, k_prefix, v_prefix, prefix_len, k_suffix, v_suffix, suffix_len, nb,
+                                             window, max_prefix, max_suffix)
+
+
 # Any T tokens per sequence against the cache (csrc/extend_attention.hip): a new turn on an existing cache, a prompt
 # prefilled in pieces.
 EXTEND_TQ = 16  # csrc/kernels.h kExtendTQ: the tokens of one block's query tile

@@ -53,6 +53,9 @@ def parse_args(argv=None):
     ap.add_argument("--num_return_sequences", type=int, default=1, help="beams returned per prompt, best first")
     ap.add_argument("--length_penalty", type=float, default=1.0)
     ap.add_argument("--early_stopping", action="store_true")
+    ap.add_argument("--beam_cache", default="repeated", choices=("repeated", "shared"),
+                    help="with --num_beams: 'shared' keeps the prompt's cache once per prompt and lets its beams share it "
+                         "(fused.shared_prefix_attention) instead of one copy per beam")
     ap.add_argument("--assistant_model", default=None,
                     help="a smaller model (name or directory) with the same vocabulary: greedy speculative decoding, "
                          "or speculative sampling with --do_sample --sampler speculative")
@@ -132,7 +135,7 @@ def main(argv=None):
                          early_stopping=a.early_stopping, assistant_model=assistant,
                          num_assistant_tokens=a.num_assistant_tokens, return_dict_in_generate=assistant is not None,
                          kv_cache_dtype=a.kv_cache_dtype, prefill_chunk_size=a.prefill_chunk_size,
-                         sampler=a.sampler)
+                         sampler=a.sampler, beam_cache=a.beam_cache)
     sync()
     dt = time.perf_counter() - t0
     spec = None

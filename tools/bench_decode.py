@@ -458,10 +458,60 @@ def reorder_times(model, rows, num_beams, prompt, new, iters=50):
     return out
 
 
-def beam_end_to_end(name, dev, num_beams):
+SHARED_HEADS = [("gpt2", 12, 12, 64), ("llama-3-8b", 32, 8, 128)]
+
+
+def beam_shared_table(dev, iters, Bp=2, suffix=64):
+    """fused.shared_prefix_attention (one prefix cache row per prompt, csrc/prefix_attention.hip) against
+    fused.decode_attention on the repeated cache (one row per beam) at the same prompt / suffix lengths: both over
+    distinct caches that sweep 3 x 256 MiB per measurement, alternating, the better of two rounds each."""
+    lines = [f"{'heads':>11s} {'Bp':>3s} {'beams':>5s} {'prompt':>6s} {'suffix':>6s} {'S1+S2':>6s} {'repeated us':>11s} "
+             f"{'shared us':>10s} {'shared / repeated':>17s} {'max |diff|':>10s}"]
+    for name, H, Hkv, D in SHARED_HEADS:
+        for nb in (4, 8):
+            for L in (2048, 16384):
+                rows = Bp * nb
+                g = torch.Generator(device=dev).manual_seed(0)
+
+                def variants(row_bytes):
+                    return max(2, min(64, -(-3 * CACHE_BYTES // row_bytes)))
+
+                n_s = variants(2 * Bp * Hkv * L * D * 2)
+                n_r = variants(2 * rows * Hkv * (L + suffix) * D * 2)
+                pre = [torch.randn(2, Bp, L, Hkv, D, device=dev, dtype=torch.bfloat16, generator=g) for _ in range(n_s)]
+                suf = torch.randn(2, rows, suffix, Hkv, D, device=dev, dtype=torch.bfloat16, generator=g)
+                full = [torch.empty(2, rows, L + suffix, Hkv, D, device=dev, dtype=torch.bfloat16) for _ in range(n_r)]
+                for i, c in enumerate(full):  # the repeated cache of prefix variant i: the same keys, nb copies
+                    c[:, :, :L] = pre[i % n_s].repeat_interleave(nb, dim=1)
+                    c[:, :, L:] = suf
+                q = torch.randn(rows, H, D, device=dev, dtype=torch.bfloat16, generator=g)
+                plen = torch.full((Bp,), L, dtype=torch.int32, device=dev)
+                slen = torch.full((rows,), suffix, dtype=torch.int32, device=dev)
+                tlen = torch.full((rows,), L + suffix, dtype=torch.int32, device=dev)
+
+                def shared(i):
+                    return fused.shared_prefix_attention(q, pre[i][0], pre[i][1], plen, suf[0], suf[1], slen, nb)
+
+                def repeated(i):
+                    return fused.decode_attention(q, full[i][0], full[i][1], tlen, 0, L + suffix)
+
+                err = float((shared(0).float() - repeated(0).float()).abs().max())
+                t_s, t_r = [], []
+                for _ in range(2):
+                    t_r.append(_time(repeated, n_r, iters))
+                    t_s.append(_time(shared, n_s, iters))
+                (s1, _), (s2, _) = fused.shared_prefix_splits(Bp, nb, Hkv, L, suffix)
+                lines.append(f"{name:>11s} {Bp:3d} {nb:5d} {L:6d} {suffix:6d} {s1:3d}+{s2:<2d} {min(t_r) * 1e6:11.1f} "
+                             f"{min(t_s) * 1e6:10.1f} {min(t_s) / min(t_r):17.3f} {err:10.1e}")
+                del pre, full, suf
+                torch.cuda.empty_cache()
+    return lines
+
+
+def beam_end_to_end(name, dev, num_beams, shared=False, prompt=None):
     """Beam search at B / num_beams prompts against greedy at B rows on the same model: the decode kernels and
-    the GEMMs see the same M."""
-    s = E2E[name]
+    the GEMMs see the same M.  ``shared``: also beam search with ``beam_cache="shared"``, alternating with the others."""
+    s = dict(E2E[name], **({} if prompt is None else {"prompt": prompt}))
     cfg = load_config(s["model"])
     torch.manual_seed(0)
     with torch.device(dev):
@@ -476,8 +526,11 @@ def beam_end_to_end(name, dev, num_beams):
     model.generate(ids[:Bb], max_new_tokens=8, **kw)  # warm-up: code objects, GEMM algorithm choices
     per = {}
     for rnd in range(2):  # the two alternate; the better round of each is reported, both are printed
-        for what, call in (("greedy", lambda n: model.generate(ids, max_new_tokens=n)),
-                           ("beam", lambda n: model.generate(ids[:Bb], max_new_tokens=n, **kw))):
+        calls = [("greedy", lambda n: model.generate(ids, max_new_tokens=n)),
+                 ("beam", lambda n: model.generate(ids[:Bb], max_new_tokens=n, **kw))]
+        if shared:
+            calls.append(("shared", lambda n: model.generate(ids[:Bb], max_new_tokens=n, beam_cache="shared", **kw)))
+        for what, call in calls:
             t, out = _wall(lambda: call(new))
             assert out.shape == (rows, s["prompt"] + new), out.shape
             t1, _ = _wall(lambda: call(1))
@@ -486,6 +539,9 @@ def beam_end_to_end(name, dev, num_beams):
                          f"{per[what][-1]:.3f} ms per step")
     g, b = min(per["greedy"]), min(per["beam"])
     lines.append(f"  ms per step: beam {b:.3f}, greedy {g:.3f}, beam / greedy {b / g:.3f}")
+    if shared:
+        lines.append(f"  ms per step: beam on a shared prompt cache {min(per['shared']):.3f}, shared / repeated "
+                     f"{min(per['shared']) / b:.3f}")
     for suffix, t in reorder_times(model, rows, num_beams, s["prompt"], new):
         lines.append(f"  reorder_rows at a suffix of {suffix:3d} positions: {t * 1e6:8.1f} us, {t * 1e3 / b:6.1%} of a beam step")
     del model
@@ -554,6 +610,10 @@ def main(argv=None):
     ap.add_argument("--kv_cache_dtype", default=None, choices=("fp8_e4m3",),
                     help="the kernel table's fp8 axis: cached_attention_fp8 (csrc/kv8_attention.hip) at T = 1 / 5 / 8 "
                          "against decode_attention / chunk_attention on a bf16 cache of the same shape")
+    ap.add_argument("--beam_cache", default="repeated", choices=("repeated", "shared"),
+                    help="shared: the shared-prefix attention table (csrc/prefix_attention.hip against decode_attention "
+                         "on the repeated cache) and, with --num_beams, beam search end to end both ways")
+    ap.add_argument("--e2e_prompt", type=int, default=None, help="with --num_beams: the prompt length, instead of the preset's")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("bench_decode.py measures on the GPU; there is none here")
@@ -570,6 +630,12 @@ def main(argv=None):
         print("\n".join(head), flush=True)
         report += head + kv8_table(dev, a.iters) + [""]
         print("\n".join(report[-len(KERNEL_SHAPES) * 3 - 2:]), flush=True)
+    if a.beam_cache == "shared":
+        head = ["## shared_prefix_attention (csrc/prefix_attention.hip) against decode_attention on the repeated cache, "
+                "bf16, every row at full length; back-to-back calls between device events", ""]
+        print("\n".join(head), flush=True)
+        report += head + beam_shared_table(dev, a.iters) + [""]
+        print("\n".join(report[-10:]), flush=True)
     if not a.skip_skinny:
         head = ["## skinny-M GEMM (csrc/skinny_gemm.hip), weight bytes over device time (summed kernel durations of a "
                 f"profiler trace) against the {HBM_COPY_TBS} TB/s float4 copy; 4-bit bytes are {W4_BYTES} per element", ""]
@@ -591,7 +657,7 @@ def main(argv=None):
         report += ["## end to end", ""]
         for name in a.e2e or sorted(E2E):
             if a.num_beams > 1:
-                lines = beam_end_to_end(name, dev, a.num_beams)
+                lines = beam_end_to_end(name, dev, a.num_beams, a.beam_cache == "shared", a.e2e_prompt)
             else:
                 lines = end_to_end(name, dev, a.naive_steps, a.ab)
             print("\n".join(lines), flush=True)
